@@ -2,6 +2,7 @@
 """bench.py -- point-clouds/sec of the EPN hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--model cls|reg|inv] [--dtype f32|bf16] [--forward-only]
+                    [--dump-outputs DIR] [--full]
 
 With N > 1 and no launcher environment the script starts its own N ranks (one process per GPU, dp.launch);
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...` works
@@ -15,6 +16,13 @@ Workloads (BASELINE.json `configs`):
   inv --dtype bf16 (configs[3]): 3DMatch descriptor, 64 patches, N=2048, bf16 features.
 Random-init weights, synthetic unit-ball clouds and labels already resident in HBM.  One step = forward + loss + backward
 (+ gradient all-reduce over RCCL when N > 1) + Adam update.  Weak scaling: per-GPU batch fixed.  Prints ONE JSON line.
+
+A plain run measures the headline only: set up, warm up, time K steps, print the line.  --full adds everything else the
+benchmark reports: the per-kernel roofline (eager steps timed call by call after the timed region), the other fp32 GEMM
+forms, the index kernels alone, the other BASELINE configs, the rank program of a multi-GPU job, the comm-free step time of
+every rank (N > 1) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (loss, network outputs, gradients, parameters after the update)
+as DIR/<name>.npy, so that two builds can be compared output for output (inputs and weights are seeded).
 """
 import argparse
 import json
@@ -117,7 +125,7 @@ def norm_kernel_name(name):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="clouds per GPU (default: 32 for cls, 64 for reg / inv)")
     ap.add_argument("--points", type=int, default=0, help="points per cloud (default: 1024; 2048 for inv)")
@@ -136,8 +144,8 @@ def parse():
     ap.add_argument("--backbone-only", action="store_true", help="without the output head")
     ap.add_argument("--model", default="cls", choices=["cls", "reg", "inv"])
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the other single-GPU configs (cls forward only, reg bf16, inv bf16) that the default run "
-                         "embeds under \"configs\"")
+                    help="skip the other single-GPU configs (cls forward only, reg bf16, inv bf16) that a --full run of "
+                         "the default workload embeds under \"configs\"")
     ap.add_argument("--dp-path", action="store_true",
                     help="run the program ONE RANK of a multi-GPU job runs, on a single GPU: gradients gathered into the flat "
                          "GradBuckets buffer, the all-reduce issued on a 1-rank RCCL communicator after every replay, inside the "
@@ -150,7 +158,17 @@ def parse():
                          "tools/nan_hunt.sh)")
     ap.add_argument("--policy", default="", help="A/B switch of the tuning tools: epn_set_kernel_policy value (e.g. 0x401), see "
                                                  "include/epn_so3conv.h; default = the library's own choices")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel roofline, the other fp32 forms, index "
+                         "kernels, the other single-GPU configs, the rank program and the CPU baseline (the --no-* options "
+                         "switch parts of it off)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in "
+                         "all: larger arrays are a fixed, seeded sample)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def usable_cpus():
@@ -455,10 +473,60 @@ def hold_gpu(ms, dev):
     torch.cuda._sleep(int(ms * _SLEEP_CYCLES_PER_MS))
 
 
+DUMP_LIMIT_BYTES = 60 * 2 ** 20     # --dump-outputs: all files together (under 64 MB with the .npy headers)
+DUMP_SEED = 2913
+
+
+def _host(t):
+    """Tensor -> host array: float64 stays float64, every other type becomes float32."""
+    return t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+
+
+def _output_leaves(o, name):
+    """(name, tensor) of every tensor in a network output: a tensor, a tuple / list of outputs or a SphericalPointCloud."""
+    if torch.is_tensor(o):
+        yield name, o
+    elif isinstance(o, (tuple, list)):
+        for i, v in enumerate(o):
+            yield from _output_leaves(v, f"{name}_{i}")
+    elif o is not None:
+        for k in ("xyz", "feats"):
+            if torch.is_tensor(getattr(o, k, None)):
+                yield f"{name}_{k}", getattr(o, k)
+
+
+def step_outputs(loss, out, params, with_grads):
+    """What one step hands its caller, as host arrays: the loss, the network's outputs and, for a training step, every
+    parameter's gradient and every parameter after the optimiser update (each flattened and concatenated in parameter
+    order; a parameter without a gradient contributes zeros)."""
+    arrays = {"loss": _host(loss)}
+    arrays.update((n, _host(t)) for n, t in _output_leaves(out, "output"))
+    if with_grads:
+        arrays["grads"] = _host(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float()
+                                           for p in params]))
+        arrays["params"] = _host(torch.cat([p.detach().reshape(-1).float() for p in params]))
+    return arrays
+
+
+def write_outputs(arrays, directory):
+    """DIR/<name>.npy for every array, at most DUMP_LIMIT_BYTES in all: an array over its equal share of the limit is
+    replaced by a fixed, seeded sample of its flattened elements (the same indices for the same shape, run after run)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def measure(cfg, rank, local_rank, world, dev, first=True):
-    """One workload (cfg: model, dtype, forward_only, steps, warmup, batch, points, no_graph, backbone_only): builds the
-    network, warms up, captures the step into a HIP graph, times exactly cfg.steps steps between barrier + synchronize
-    fences (max over ranks), then profiles a few eager steps call by call.  Returns (json_dict, handles) on every rank."""
+    """One workload (cfg: model, dtype, forward_only, steps, warmup, batch, points, no_graph, backbone_only, full,
+    dump_outputs): builds the network, warms up, captures the step into a HIP graph, times exactly cfg.steps steps between
+    barrier + synchronize fences (max over ranks), then (cfg.full) profiles a few eager steps call by call.  Returns
+    (json_dict, handles) on every rank; handles["outputs"] (rank 0, cfg.dump_outputs) = step_outputs() of the last timed step."""
     from epn_pointcloud_amd import dp, models as M, ops, schedule as S
     from epn_pointcloud_amd import gemm as _gemm
     TRACE = bool(getattr(cfg, "trace_loss", False))
@@ -509,18 +577,27 @@ def measure(cfg, rank, local_rank, world, dev, first=True):
     buckets = (dp.GradBuckets(dp.stage_buckets(model), world, hooks=False, collect=collect, force_collectives=dp_path)
                if not cfg.forward_only and (world > 1 or dp_path) else None)
     calls = [0]
+    full = bool(getattr(cfg, "full", False))
+    dump = bool(getattr(cfg, "dump_outputs", ""))
+    outs = [None]                       # --dump-outputs: the network's outputs of the latest step (static ones once captured)
+
+    def forward():
+        out = model(pts)
+        if dump:
+            outs[0] = out
+        return out
 
     def compute():                      # the hot path: forward (+ loss + backward)
         calls[0] += 1
         if cfg.forward_only:
             with torch.no_grad():
-                return loss_of(model(pts))
+                return loss_of(forward())
         if buckets is not None:
             buckets.zero()
         else:
             for p in params:
                 p.grad = None
-        loss = loss_of(model(pts))
+        loss = loss_of(forward())
         loss.backward()
         if buckets is not None:
             buckets.pack()              # (pack form) the step's gradients -> the flat buffer, one multi-tensor copy
@@ -600,7 +677,7 @@ def measure(cfg, rank, local_rank, world, dev, first=True):
     _gemm.fixed_point_range_count(reset=True)    # ... and the range sentinel of the fixed-point transpose of the grouping
     if buckets is not None:
         buckets.record_timing, buckets.timings = True, []
-    if graph is None:
+    if graph is None and full:
         ops.profile_begin()                      # eager: HIP events around every call of the timed region itself
     t0 = time.perf_counter()
     for _ in range(cfg.steps):
@@ -611,6 +688,9 @@ def measure(cfg, rank, local_rank, world, dev, first=True):
     dt_local = time.perf_counter() - t0          # this rank's own time, before it waits for the others
     fence()
     dt = time.perf_counter() - t0
+    # what the last timed step handed its caller, copied to the host before anything below runs the network again
+    dumped = (step_outputs(last, outs[0], params, with_grads=not cfg.forward_only)
+              if dump and rank == 0 else None)
     # ---- what a multi-rank line needs to explain itself (world > 1, or the rank program on one GPU): per-rank step time,
     # the collective phase as the compute stream sees it, its bus bandwidth, and the same step WITHOUT the collective timed
     # right here on every rank at once (so the comparison shares this run's clocks, power state and neighbours)
@@ -627,7 +707,8 @@ def measure(cfg, rank, local_rank, world, dev, first=True):
                    "bus_gbps": round(2.0 * (world - 1) / max(world, 1) * nbytes / max(ar, 1e-6) / 1e6, 1) if world > 1 else None}
 
         dp_info["no_comm_ms_per_step_local"] = None
-        if graph is not None:                    # (eager mode issues its collectives from backward hooks: no comm-free form)
+        comm_free = graph is not None and full   # (eager mode issues its collectives from backward hooks: no comm-free form)
+        if comm_free:
             fence()
             t1 = time.perf_counter()
             for _ in range(cfg.steps):           # the rank program minus its collective (replicas drift: timing only)
@@ -643,11 +724,14 @@ def measure(cfg, rank, local_rank, world, dev, first=True):
             torch.distributed.all_gather(allr, mine)
             rows = torch.stack(allr).cpu()
             dp_info["per_rank_ms_per_step"] = [round(float(rows[:, 0].min()), 3), round(float(rows[:, 0].max()), 3)]
-            if graph is not None:
+            if comm_free:
                 dp_info["per_rank_no_comm_ms"] = [round(float(rows[:, 1].min()), 3), round(float(rows[:, 1].max()), 3)]
             dp_info["per_rank_allreduce_ms"] = [round(float(rows[:, 2].min()), 3), round(float(rows[:, 2].max()), 3)]
-            dp.broadcast_parameters(model)       # re-synchronise the replicas the comm-free steps let drift
-    if graph is None:
+            if comm_free:
+                dp.broadcast_parameters(model)   # re-synchronise the replicas the comm-free steps let drift
+    if not full:
+        records = None                           # the per-kernel roofline: --full only
+    elif graph is None:
         records, prof_steps = ops.profile_end(), cfg.steps
     else:
         # graph replays have no host-side launch points: for the roofline the same step runs eagerly, timed call by
@@ -712,7 +796,9 @@ def measure(cfg, rank, local_rank, world, dev, first=True):
         slow = dp_info.get("per_rank_no_comm_ms", [None, dp_info["no_comm_ms_per_step_local"]])[1]
         dp_info["eff_vs_rank_program"] = round(slow / (dt / cfg.steps * 1e3), 4) if slow else None
         out["dp"] = dp_info
-    if rank == 0:
+    if rank == 0 and not full:
+        detail = {}
+    elif rank == 0:
         # PMC passes exist for the cls fp32 step (B=32) and the rotation network's bf16 step (B=64): their kernels' traffic
         profiled = (not cfg.forward_only) and ((cfg.model, batch, dtype_name) in (("cls", 32, "f32"), ("reg", 64, "bf16"),
                                                                                   ("inv", 64, "bf16")))
@@ -731,12 +817,13 @@ def measure(cfg, rank, local_rank, world, dev, first=True):
             if gb:
                 st["hbm_gb"], st["hbm_over_algorithmic"] = gb, round(gb * 1e9 / by, 1)
             out["roofline"]["step"] = st
-        detail["compute_calls"] = calls[0]
-        print(f"[bench] compute_calls {calls[0]}", file=sys.stderr)
     else:
         detail = None
+    if rank == 0:
+        detail["compute_calls"] = calls[0]
+        print(f"[bench] compute_calls {calls[0]}", file=sys.stderr)
     handles = dict(detail=detail, model=model, layers=layers, flat_pts=flat_pts, compute=compute, finish=finish, opt=opt, graph=graph,
-                   head=head, points=points, batch=batch, split_gemm=split_gemm)
+                   head=head, points=points, batch=batch, split_gemm=split_gemm, outputs=dumped)
     return out, handles
 
 
@@ -888,9 +975,11 @@ def main():
         _lib.check(_lib.get_lib().epn_set_kernel_policy(int(args.policy, 0)), "set_kernel_policy")
 
     out, H = measure(args, rank, local_rank, world, dev)
+    if H["outputs"] is not None:
+        write_outputs(H["outputs"], args.dump_outputs)
     detail = {"headline": H["detail"]}
     cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from epn_pointcloud_amd import gemm as _gemm
         if world == 1 and H["split_gemm"] and not args.no_native_line:
             # the same step with the weight contractions / basis change in the OTHER fp32 forms (gemm.FP32_MODES: the fp32
@@ -944,7 +1033,7 @@ def main():
     default_run = (args.model == "cls" and not args.dtype and not args.forward_only and not args.backbone_only
                    and not args.batch and not args.points)
     H.clear()
-    if world == 1 and default_run and not args.no_extra_configs:
+    if world == 1 and default_run and args.full and not args.no_extra_configs:
         # The other single-GPU BASELINE configs, in the SAME run so that they carry the driver's clock: configs[1] forward
         # only (north_star states its >= 10x CPU target on the forward pass), configs[2] (rotation estimation, bf16) and
         # configs[3] (3DMatch descriptor, bf16): 10 graph replays each, own roofline objects.
@@ -955,7 +1044,7 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
             c = copy.copy(args)
-            c.model, c.forward_only, c.dtype, c.batch, c.points = model, fwd, "", 0, 0
+            c.model, c.forward_only, c.dtype, c.batch, c.points, c.dump_outputs = model, fwd, "", 0, 0, ""
             c.steps, c.warmup = min(args.steps, 10), min(args.warmup, 2)
             try:
                 o, h = measure(c, rank, local_rank, world, dev, first=False)
@@ -971,7 +1060,7 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
             c = copy.copy(args)
-            c.dp_path, c.warmup = True, min(args.warmup, 2)
+            c.dp_path, c.warmup, c.dump_outputs = True, min(args.warmup, 2), ""
             try:
                 o, h = measure(c, rank, local_rank, world, dev, first=False)
                 grad_mb = sum(p.numel() for p in h["model"].parameters() if p.requires_grad) * 4 / 1e6

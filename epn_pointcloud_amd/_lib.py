@@ -35,7 +35,7 @@ EXPORTS = [
     "epn_inter_bwd_data_f16x2_f32", "epn_inter_ungroup_cloud_ok", "epn_inter_ungroup_cloud_workspace_bytes", "epn_inter_ungroup_cloud_f32",
     "epn_inter_ungroup_cloud_bf16", "epn_inter_ungroup_cloud_range_count", "epn_gemm_nt_f16x2_workspace_bytes", "epn_gemm_nt_f16x2_f32", "epn_gemm_tn_f16x2_f32", "epn_gemm_tn_grouped_f16x2",
     "epn_inter_group_bf16", "epn_inter_ungroup_bf16", "epn_intra_group_bf16", "epn_so3_basis_bf16",
-    "epn_gather_rows", "epn_scatter_rows", "epn_conv1x1_c1_f32", "epn_conv1x1_c1_bwd_weight_f32",
+    "epn_gather_rows", "epn_scatter_rows", "epn_conv1x1_c1_f32", "epn_conv1x1_c1_bwd_weight_f32", "epn_conv1x1_c1_bwd_weight_ws_f32",
     "epn_anchor_softmax_pool_fwd_f32", "epn_anchor_softmax_pool_bwd_f32",
     "epn_ball_query_f64", "epn_fps_f64", "epn_gather_fwd_f64", "epn_gather_bwd_f64", "epn_so3_basis_norm_f32", "epn_so3_basis_norm_bf16", "epn_so3_basis_split_f32", "epn_so3_basis_norm_split_f32", "epn_inter_inverse_list", "epn_inter_ungroup_det_f32", "epn_inter_ungroup_det_bf16",
     "epn_chan_stats_bf16", "epn_norm_act_fwd_bf16", "epn_norm_act_bwd_reduce_bf16", "epn_norm_act_bwd_apply_bf16",
@@ -263,6 +263,7 @@ def get_lib():
     lib.epn_scatter_rows_add.restype = _ci
     lib.epn_conv1x1_c1_f32.argtypes = [_vp, _vp, _vp, _ll, _ci, _vp]
     lib.epn_conv1x1_c1_bwd_weight_f32.argtypes = [_vp, _vp, _vp, _ll, _ci, _vp]
+    lib.epn_conv1x1_c1_bwd_weight_ws_f32.argtypes = [_vp, _vp, _vp, _ll, _ci, _vp, _sz, _vp]
     lib.epn_anchor_softmax_pool_fwd_f32.argtypes = [_vp, _vp, _vp, _vp, _ll, _ci, _ci, _vp]
     lib.epn_anchor_softmax_pool_bwd_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _ci, _ci, _vp]
     lib.epn_gather_rows.restype = lib.epn_scatter_rows.restype = _ci

@@ -1124,7 +1124,9 @@ __global__ __launch_bounds__(256) void c1_outer_kernel(const float *__restrict__
     y[i] = f32x4{xv * wv[0], xv * wv[1], xv * wv[2], xv * wv[3]};
 }
 
-// block = (c/4 channel lanes) x (256 / (c/4) row lanes); per-channel partial sums, LDS tree, one atomic per channel and block
+// block = (c/4 channel lanes) x (256 / (c/4) row lanes); per-channel partial sums, LDS tree, then one atomic per channel
+// and block (PARTS = false) or the block's partials stored to dw[block][c] for c1_outer_bwd_finish_kernel (PARTS = true)
+template <bool PARTS>
 __global__ __launch_bounds__(256) void c1_outer_bwd_kernel(const float *__restrict__ x, const f32x4 *__restrict__ dy,
                                                            float *__restrict__ dw, long long rows, int c4,
                                                            long long rows_per_block) {
@@ -1147,9 +1149,23 @@ __global__ __launch_bounds__(256) void c1_outer_bwd_kernel(const float *__restri
         for (int t = 1; t < rstep; ++t)
 #pragma unroll
             for (int i = 0; i < 4; ++i) s[i] += red[t * c4 + cl][i];
+        if constexpr (PARTS) {
+            reinterpret_cast<f32x4 *>(dw)[(size_t)blockIdx.x * c4 + cl] = s;
+        } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) atomicAdd(dw + 4 * cl + i, s[i]);
+            for (int i = 0; i < 4; ++i) atomicAdd(dw + 4 * cl + i, s[i]);
+        }
     }
+}
+
+// dw[c] = the per-block partials of c1_outer_bwd_kernel<true> summed in block order (bitwise repeatable)
+__global__ __launch_bounds__(256) void c1_outer_bwd_finish_kernel(const float *__restrict__ part, float *__restrict__ dw,
+                                                                  int nblocks, int cout) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cout) return;
+    float s = 0.f;
+    for (int b = 0; b < nblocks; ++b) s += part[(size_t)b * cout + c];
+    dw[c] = s;
 }
 }  // namespace
 }  // namespace epn
@@ -1175,8 +1191,31 @@ extern "C" int epn_conv1x1_c1_bwd_weight_f32(const float *x, const float *grad_y
     if (!x || !grad_y) return EPN_ENULL;
     const long long blocks = rows < 1024 * 64 ? (rows + 63) / 64 : 1024;
     const long long rpb = (rows + blocks - 1) / blocks;
-    EPN_LAUNCH(epn::c1_outer_bwd_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, st, x,
+    EPN_LAUNCH(epn::c1_outer_bwd_kernel<false>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, st, x,
                        reinterpret_cast<const f32x4 *>(grad_y), grad_w, rows, cout / 4, rpb);
+    EPN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int epn_conv1x1_c1_bwd_weight_ws_f32(const float *x, const float *grad_y, float *grad_w, long long rows, int cout,
+                                                 void *workspace, size_t workspace_bytes, epn_stream_t stream) {
+    if (rows < 0 || cout < 4 || cout % 4 || cout > 1024 || 256 % (cout / 4)) return EPN_EINVAL;
+    if (!grad_w) return EPN_ENULL;
+    hipStream_t st = epn_stream(stream);
+    if (rows == 0) {
+        EPN_HIP(hipMemsetAsync(grad_w, 0, sizeof(float) * cout, st));
+        return 0;
+    }
+    if (!x || !grad_y) return EPN_ENULL;
+    const long long blocks = rows < 1024 * 64 ? (rows + 63) / 64 : 1024;
+    const long long rpb = (rows + blocks - 1) / blocks;
+    const long long nb = (rows + rpb - 1) / rpb;                  // <= blocks <= 1024
+    if (!workspace || (uintptr_t)workspace % 16 || workspace_bytes < (size_t)nb * cout * sizeof(float)) return EPN_EWORKSPACE;
+    EPN_LAUNCH(epn::c1_outer_bwd_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, x,
+                       reinterpret_cast<const f32x4 *>(grad_y), static_cast<float *>(workspace), rows, cout / 4, rpb);
+    EPN_CHECK_LAUNCH();
+    EPN_LAUNCH(epn::c1_outer_bwd_finish_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, st,
+                       static_cast<const float *>(workspace), grad_w, (int)nb, cout);
     EPN_CHECK_LAUNCH();
     return 0;
 }

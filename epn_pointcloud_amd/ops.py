@@ -1905,7 +1905,8 @@ def anchor_softmax_pool(feats, logits):
 
 class Conv1x1C1Fn(torch.autograd.Function):
     """nn.Conv2d(1, cout, 1) on channels-last rows: y[row][c] = x[row] * w[c] (epn_conv1x1_c1_f32); the weight gradient is
-    one streaming reduction (epn_conv1x1_c1_bwd_weight_f32).  x is the occupancy feature of the first block (an input)."""
+    one streaming reduction with per-block partials summed in a fixed order (epn_conv1x1_c1_bwd_weight_ws_f32: bitwise
+    repeatable).  x is the occupancy feature of the first block (an input)."""
 
     @staticmethod
     def forward(ctx, x_rows, w):
@@ -1925,8 +1926,10 @@ class Conv1x1C1Fn(torch.autograd.Function):
         gx = gw = None
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(w)
-            _lib.check(lib.epn_conv1x1_c1_bwd_weight_f32(x_rows.data_ptr(), gy.data_ptr(), gw.data_ptr(), x_rows.numel(),
-                                                         w.numel(), _lib.stream_of(gy)), "conv1x1_c1_bwd_weight")
+            ws = torch.empty(1024 * w.numel(), dtype=torch.float32, device=gy.device)     # partials: <= 1024 blocks x cout
+            _lib.check(lib.epn_conv1x1_c1_bwd_weight_ws_f32(x_rows.data_ptr(), gy.data_ptr(), gw.data_ptr(), x_rows.numel(),
+                                                            w.numel(), ws.data_ptr(), ws.numel() * 4, _lib.stream_of(gy)),
+                       "conv1x1_c1_bwd_weight")
         if ctx.needs_input_grad[0]:
             gx = gy @ w
         return gx, gw

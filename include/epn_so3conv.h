@@ -784,10 +784,17 @@ int epn_scatter_rows_add(const void *grad_dst, const int32_t *idx, void *grad_sr
 /* 1x1 convolution of a SINGLE input channel (the skip branch of every model's first block, whose input is the
  * occupancy feature: nn.Conv2d(1, cout, 1), SPConvNets/utils/base_so3conv.py:186): y[row][c] = x[row] * w[c], rows =
  * b*p*a of the channels-last tensor, cout % 4 == 0; and its weight gradient grad_w[c] = sum_row x[row] * grad_y[row][c]
- * (zero-fills grad_w first; 256 % (cout/4) == 0). */
+ * (zero-fills grad_w first; 256 % (cout/4) == 0).  epn_conv1x1_c1_bwd_weight_f32 adds its per-block partials with fp32
+ * atomics, in an order that varies from call to call; epn_conv1x1_c1_bwd_weight_ws_f32 stores them to `workspace` (16-byte
+ * aligned, at least EPN_CONV1X1_C1_WS_BYTES(cout) bytes; EPN_EWORKSPACE below what the call needs) and sums them in a fixed
+ * order: bitwise repeatable.  Behind an instance norm the gradient is a near-cancelling sum, where the atomics' order moves
+ * it by tens of percent. */
+#define EPN_CONV1X1_C1_WS_BYTES(cout) ((size_t)1024 * (size_t)(cout) * sizeof(float))
 int epn_conv1x1_c1_f32(const float *x, const float *w, float *y, long long rows, int cout, epn_stream_t stream);
 int epn_conv1x1_c1_bwd_weight_f32(const float *x, const float *grad_y, float *grad_w, long long rows, int cout,
                                   epn_stream_t stream);
+int epn_conv1x1_c1_bwd_weight_ws_f32(const float *x, const float *grad_y, float *grad_w, long long rows, int cout,
+                                     void *workspace, size_t workspace_bytes, epn_stream_t stream);
 
 /* Attention pooling over the anchors in the 3DMatch head: replaces `attn = F.softmax(attn, dim=3)` and
  * `x_out = (x.feats * attn).sum(-1, keepdim=True)` of InvOutBlockMVD.forward (SPConvNets/utils/base_so3conv.py:603-606)

@@ -186,3 +186,35 @@ def test_an_oversized_line_is_trimmed_not_printed():
     text = bench.fit_line(bench.compact_line(out))
     line = json.loads(text)
     assert len(text) < bench.LINE_LIMIT and "roofline" in line and "cpu_baseline" in line and line["value"] == out["value"]
+
+
+def test_dumped_outputs_stay_under_the_limit_and_sample_the_same_elements(tmp_path):
+    """--dump-outputs: loss, network outputs (tuples and point clouds flattened to named leaves), gradients and parameters as
+    float32 (float64 kept), at most 64 MB in all; an array over its share is a seeded sample -- the same elements every run."""
+    import numpy as np
+    import torch
+
+    class Cloud:
+        def __init__(self, xyz, feats):
+            self.xyz, self.feats = xyz, feats
+
+    big = torch.nn.Parameter(torch.arange(9 * 2 ** 20, dtype=torch.float32))
+    small = torch.nn.Parameter(torch.ones(3, dtype=torch.float64))
+    big.grad = -big.detach()
+    out = (torch.ones(2, 4, dtype=torch.bfloat16), Cloud(torch.zeros(1, 3, 5), torch.full((1, 2, 5, 60), 2.0, dtype=torch.float64)))
+    arrays = bench.step_outputs(torch.tensor(0.5), out, [big, small], with_grads=True)
+    assert set(arrays) == {"loss", "output_0", "output_1_xyz", "output_1_feats", "grads", "params"}
+    assert arrays["output_0"].dtype == np.float32 and arrays["output_1_feats"].dtype == np.float64
+    assert arrays["grads"].size == 9 * 2 ** 20 + 3 and not arrays["grads"][-3:].any()       # no gradient: zeros
+    runs = []
+    for d in ("a", "b"):
+        bench.write_outputs(arrays, str(tmp_path / d))
+        runs.append({f.name: np.load(f) for f in (tmp_path / d).iterdir()})
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 64e6
+    a, b = runs
+    assert set(a) == {n + ".npy" for n in arrays} and a["loss.npy"] == np.float32(0.5)
+    assert a["params.npy"].size < arrays["params"].size and np.array_equal(a["params.npy"], b["params.npy"])
+    g, p = a["grads.npy"], a["params.npy"]
+    assert np.all((g == -p) | (g == 0))                      # same length, same elements: gradient and parameter side by side
+    assert np.all(np.diff(p[p > 1.5]) > 0)                   # sampled in element order
+    assert np.array_equal(a["output_1_feats.npy"], arrays["output_1_feats"])                  # small arrays: whole

@@ -1206,3 +1206,23 @@ def test_first_layer_weight_gradient_from_saved_grouped_values(gpu, vgtk_alias, 
     (dWo,) = torch.autograd.grad(oo, [wo], gout.cpu())
     assert torch.allclose(o1.cpu(), oo.detach(), atol=TOL)
     assert _rel(g1.cpu(), dWo) < TOL
+
+
+@pytest.mark.parametrize("rows,cout", [(32 * 1024 * 60, 64), (1000, 128), (77, 4)])
+def test_c1_conv_weight_gradient_is_bitwise_repeatable(gpu, rows, cout):
+    """The 1x1 convolution of the single occupancy channel (every first block's skip branch): its weight gradient is a sum over
+    all rows, which an instance norm behind the conv makes near-cancelling -- a summation order that varies from call to call
+    moved it by tens of percent, and Adam carried that into the whole network.  The per-block partials are summed in a fixed
+    order: two calls on the same inputs agree bit for bit, and the sum matches fp64."""
+    from epn_pointcloud_amd import ops
+    torch.manual_seed(rows + cout)
+    x = torch.rand(rows, device=gpu)
+    w = torch.randn(cout, device=gpu, requires_grad=True)
+    gy = torch.randn(rows, cout, device=gpu)
+    gy = gy - gy.mean(0, keepdim=True)                  # near-cancelling columns, as behind a norm
+    y = ops.Conv1x1C1Fn.apply(x, w)
+    assert torch.equal(y, x[:, None] * w.detach()[None, :])
+    g = [torch.autograd.grad(ops.Conv1x1C1Fn.apply(x, w), [w], gy)[0] for _ in range(3)]
+    assert torch.equal(g[0], g[1]) and torch.equal(g[0], g[2])
+    want = (x.double()[:, None] * gy.double()).sum(0)
+    assert (g[0].double() - want).abs().max().item() <= 1e-5 * (x.double()[:, None] * gy.double()).abs().sum(0).max().item()

@@ -406,7 +406,7 @@ def test_bench_line_kernel_names_are_profiler_names(gpu, tmp_path):
         pytest.skip("profiles/r0N_kernel_stats.csv not collected yet")
     known = {bench.norm_kernel_name(r["Name"]) for r in csv.DictReader(open(stats))}
     detail_file = str(tmp_path / "bench_detail.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                           "--no-native-line", "--no-extra-configs"], capture_output=True, text=True, timeout=900,
                          env=dict(os.environ, EPN_BENCH_DETAIL=detail_file))
     assert out.returncode == 0, out.stderr[-2000:]
@@ -428,7 +428,7 @@ def test_bench_line_kernel_names_are_profiler_names(gpu, tmp_path):
 
 
 def test_default_bench_run_prints_one_small_parsable_line(gpu, tmp_path):
-    """The DEFAULT command form the driver runs (`bench.py --steps K --warmup W`, every embedded config, native line, CPU
+    """The complete command form (`bench.py --full --steps K --warmup W`, every embedded config, native line, CPU
     baseline on a one-cloud sample to keep the test short): the last stdout line parses, is < 3000 bytes and carries
     `roofline`, `cpu_baseline` and the three embedded configs with their priced dominant kernels."""
     import json
@@ -436,7 +436,7 @@ def test_default_bench_run_prints_one_small_parsable_line(gpu, tmp_path):
     import sys
     from conftest import ROOT
     detail_file = str(tmp_path / "bench_detail.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "1", "--cpu-clouds", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "1", "--cpu-clouds", "1",
                           "--cpu-samples", "1"], capture_output=True, text=True, timeout=1500,
                          env=dict(os.environ, EPN_BENCH_DETAIL=detail_file))
     assert out.returncode == 0, out.stderr[-3000:]
@@ -466,6 +466,55 @@ def test_default_bench_run_prints_one_small_parsable_line(gpu, tmp_path):
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["samples"] == 1
     # bf16 networks: the dominant GEMMs stream the grouped features -> priced against HBM
     assert line["configs"]["reg_bf16"]["bound"] == "hbm"
+
+
+def test_plain_bench_run_times_the_headline_and_dumps_its_outputs(gpu, tmp_path):
+    """The plain command form (`bench.py --gpus 1 --steps K --warmup W`) measures the headline only -- no roofline, no other
+    configs, no CPU baseline -- times exactly K steps, and with --dump-outputs writes what the last timed step computed:
+    float32 arrays, under 64 MB in all (gradients and parameters of the full-size network as a sample).  Two runs with the
+    same arguments compute the same step: same inputs, and no reduction whose summation order moves its result beyond the
+    last bits.  (Some weight gradients still add fp32 partials with atomics, e.g. the head's PointnetSO3Conv, so the runs are
+    not held to bit equality; an Adam step turns a sign flip of a near-zero gradient into a full lr-sized move of its
+    parameter, hence the parameters are compared by the fraction that moved.  The first block's skip-conv weight gradient,
+    near-cancelling and summed with atomics until it got a fixed order, left logits tens of % apart within 5 updates.)"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from conftest import ROOT
+
+    def run(dump):
+        return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                               "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900,
+                              env=dict(os.environ, EPN_BENCH_DETAIL=str(tmp_path / "bench_detail.json")))
+    dump = tmp_path / "outputs"
+    out = run(dump)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert not {"roofline", "configs", "cpu_baseline", "native_fp32_mfma", "fp32_modes", "index_kernels"} & set(line), line
+    assert line["steps"] == 5 and line["dtype"] == "f32" and line["unit"] == "point-clouds/s"
+    # steps the process executed: 2 eager warm-up steps, 1 untimed replay, the 5 timed replays (the capture executes none)
+    assert "[bench] compute_calls 8" in out.stderr, out.stderr[-2000:]
+    assert abs(line["value"] - 32 * 1e3 / line["ms_per_step"]) < 0.01 * line["value"]
+    files = {f.name: np.load(f) for f in dump.iterdir()}
+    assert {"loss.npy", "output_0.npy", "grads.npy", "params.npy"} <= set(files), sorted(files)
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64e6
+    assert files["output_0.npy"].shape == (32, 40)
+    assert all(np.isfinite(a).all() for a in files.values()) and files["grads.npy"].any()
+    again = run(tmp_path / "again")
+    assert again.returncode == 0, again.stderr[-3000:]
+    for name, a in files.items():
+        b = np.load(tmp_path / "again" / name)
+        d = np.abs(a.astype(np.float64) - b)
+        if name == "params.npy":
+            assert (d > 1e-5).mean() < 1e-3, (name, float(d.max()), float((d > 1e-5).mean()))
+        else:
+            assert d.max() <= 1e-3 * np.abs(b).max(), (name, float(d.max()), float(np.abs(b).max()))
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])

@@ -22,8 +22,8 @@ for f in kernel_stats.csv pmc_per_kernel.json bench_under_rocprof.json; do cp gp
 bash tools/replay_profile.sh ${TAG}_replay > $OUT/replay.log 2>&1
 cp gpurun_out/${TAG}_replay/per_replay.csv $OUT/per_replay_cls.csv
 # the driver's own command form first: ONE stdout line (< 3 KB) + the complete record in the detail file
-EPN_BENCH_DETAIL=$OUT/bench_cls_detail.json python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_cls.json 2> $OUT/bench_cls.err
-b() { n=$1; shift; EPN_BENCH_DETAIL=$OUT/bench_${n}_detail.json python bench.py "$@" > $OUT/bench_$n.json 2>/dev/null; }
+EPN_BENCH_DETAIL=$OUT/bench_cls_detail.json python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_cls.json 2> $OUT/bench_cls.err
+b() { n=$1; shift; EPN_BENCH_DETAIL=$OUT/bench_${n}_detail.json python bench.py --full "$@" > $OUT/bench_$n.json 2>/dev/null; }
 EPN_INTER_BWD_DATA=onchip b cls_bwd_onchip --no-cpu-baseline --no-native-line --no-extra-configs --steps 20
 b reg --model reg --dtype bf16 --no-cpu-baseline --steps 20
 b inv --model inv --dtype bf16 --no-cpu-baseline --steps 20

@@ -10,7 +10,7 @@ rm -f gpurun_out/lds_tr_probe gpurun_out/atomic_rate_probe
    "tests/test_gpu_bf16.py::test_gemm_tn_vs_fp64" "tests/test_gpu_bf16.py::test_gemm_tn_grouped" tests/test_gpu_models.py::test_full_width_cls_step_matches_oracle_loss \
    tests/test_gpu_models.py::test_pointnet_max_propagates_nan tests/test_gpu_fullsize.py tests/test_gpu_functional.py -m gpu -s 2>&1) > gpurun_out/r06_gputest_b.log 2>&1
 tail -25 gpurun_out/r06_gputest_b.log
-B="python bench.py --steps 20 --warmup 3 --no-extra-configs --no-cpu-baseline --no-native-line"
+B="python bench.py --full --steps 20 --warmup 3 --no-extra-configs --no-cpu-baseline --no-native-line"
 for i in 1 2; do
   for m in reg inv; do
     for lib in "" "_noswz"; do

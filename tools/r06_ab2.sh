@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 (timeout 900 python -m pytest -q -p no:cacheprovider tests/test_gpu_bwd_onchip.py tests/test_gpu_fullsize.py "tests/test_gpu_conv.py::test_group_ungroup_abi_vs_oracle" "tests/test_gpu_conv.py::test_ungroup_acc_adds_to_what_is_there" "tests/test_gpu_bf16.py::test_deterministic_data_gradient" tests/test_gpu_conv.py::test_shared_input_gradient_is_folded_into_the_data_gradient -m gpu 2>&1 | tail -5) | tee gpurun_out/r06_gputest_e.log
 timeout 500 python tools/bwd_onchip_probe.py cls 2>&1 | grep -v amdgpu | tee gpurun_out/r06_bwd_onchip_probe.txt
 EPN_LIB=$R/epn_pointcloud_amd/libepn_so3conv_synbar.so timeout 500 python tools/bwd_onchip_probe.py cls 2>&1 | grep -v amdgpu | tee gpurun_out/r06_bwd_onchip_probe_synbar.txt
-B="python bench.py --steps 20 --warmup 3 --no-extra-configs --no-cpu-baseline --no-native-line"
+B="python bench.py --full --steps 20 --warmup 3 --no-extra-configs --no-cpu-baseline --no-native-line"
 for i in 1 2; do
   for cfg in "cls default" "cls synbar" "cls onchip" "reg default" "reg synbar" "inv default" "inv synbar"; do
     set -- $cfg; m=$1; v=$2
