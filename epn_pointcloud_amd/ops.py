@@ -6,6 +6,7 @@ any other layout is converted once on entry.
 """
 import ctypes
 import os
+import types
 import weakref
 
 import torch
@@ -74,13 +75,41 @@ def _launch(kind, key, flops, device, fn):
     return rc
 
 
+def _run(rec, what, fn, *args):
+    """Library entry fn(*args) as ONE profiler record rec = (kind, key, flops, device), its return code checked."""
+    _lib.check(_launch(*rec, lambda: fn(*args)), what)
+
+
+def _ws(nbytes, device):
+    """Scratch memory of a library call, from the byte count its *_workspace_bytes entry gave: (tensor, void*, size_t)."""
+    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+    return ws, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())
+
+
+def _group_flops(d):
+    """Algorithmic flops of the grouping (or of its transpose): the ks x nn weights of a column, then the weighted sums."""
+    cols = float(d.b) * d.p2 * d.na
+    return 9.0 * cols * d.ks * d.nn + 2.0 * cols * d.cin * d.ks * d.nn
+
+
 def _inter_flops(d):
     cols = float(d.b) * d.p2 * d.na
-    return 9.0 * cols * d.ks * d.nn + 2.0 * cols * d.cin * d.ks * d.nn + 2.0 * cols * d.cout * d.cin * d.ks
+    return _group_flops(d) + 2.0 * cols * d.cout * d.cin * d.ks
 
 
 def _inter_key(d):
     return (d.b, d.p1, d.p2, d.nn, d.na, d.ks, d.cin, d.cout)
+
+
+def _check_inter_shapes(f, Wc, d):
+    if Wc.shape[1] != d.cin * d.ks or f.shape[2] != d.p1 or f.shape[3] != d.na or f.shape[0] != d.b:
+        raise ValueError(f"shape mismatch: feats {tuple(f.shape)}, W {tuple(Wc.shape)}, geometry "
+                         f"b={d.b} p1={d.p1} na={d.na} ks={d.ks}")
+
+
+def _check_intra_shapes(f, W, intra_idx32):
+    if W.shape[1] != f.shape[1] * intra_idx32.shape[1] or intra_idx32.shape[0] != f.shape[3]:
+        raise ValueError(f"shape mismatch: feats {tuple(f.shape)}, W {tuple(W.shape)}, intra_idx {tuple(intra_idx32.shape)}")
 
 
 FEATURE_DTYPES = (torch.float32, torch.bfloat16)
@@ -217,10 +246,22 @@ class DenseInterWeights:
         return d
 
 
-def _workspace(lib, d, device):
-    nbytes = lib.epn_inter_workspace_bytes(ctypes.byref(d))
-    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
-    return ws, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())
+def _fused_bwd_data(lib, d, g, Wc, wsp, wsn):
+    """Data gradient of the fused fp32 kernels (csrc/inter_mfma.hip); wsp, wsn: epn_inter_workspace_bytes of scratch."""
+    gf = empty_cl(d.b, d.cin, d.p1, d.na, g.device)
+    _run(("inter_bwd_data", _inter_key(d), _inter_flops(d), g.device), "inter_so3conv_bwd_data",
+         lib.epn_inter_so3conv_bwd_data_f32, ctypes.byref(d), _cl_ptr(g), _lib.dev_ptr(Wc, "W"), _cl_ptr(gf), wsp, wsn,
+         _lib.stream_of(g))
+    return gf
+
+
+def _fused_bwd_weight(lib, d, f, g, Wc, wsp, wsn):
+    """Weight gradient of the fused fp32 kernels (grouped features regenerated on chip)."""
+    gW = torch.empty_like(Wc)
+    _run(("inter_bwd_weight", _inter_key(d), _inter_flops(d), f.device), "inter_so3conv_bwd_weight",
+         lib.epn_inter_so3conv_bwd_weight_f32, ctypes.byref(d), _cl_ptr(f), _cl_ptr(g), _lib.dev_ptr(gW, "grad_W"), wsp, wsn,
+         _lib.stream_of(f))
+    return gW
 
 
 class InterSO3ConvFn(torch.autograd.Function):
@@ -232,14 +273,13 @@ class InterSO3ConvFn(torch.autograd.Function):
         lib = _lib.get_lib()
         f = to_cl(feats)
         Wc = W.contiguous()
-        cout, ck = Wc.shape
+        cout = Wc.shape[0]
         cin = f.shape[1]
         d = geo.desc(cin, cout)
-        if ck != cin * d.ks or f.shape[2] != d.p1 or f.shape[3] != d.na or f.shape[0] != d.b:
-            raise ValueError(f"shape mismatch: feats {tuple(f.shape)}, W {tuple(Wc.shape)}, geometry "
-                             f"b={d.b} p1={d.p1} na={d.na} ks={d.ks}")
+        _check_inter_shapes(f, Wc, d)
         out = empty_cl(d.b, cout, d.p2, d.na, f.device)
-        ws, wsp, wsn = _workspace(lib, d, f.device)
+        ws, wsp, wsn = _ws(lib.epn_inter_workspace_bytes(ctypes.byref(d)), f.device)
+        rec = ("inter_fwd", _inter_key(d), _inter_flops(d), f.device)
         grouped = None
         if cin == 1 and lib.epn_inter_c1_ok(ctypes.byref(d)) and ab("EPN_C1_SAVE") == "1":
             # first layer: keep the 24 grouped values per column for the weight gradient (96 B per column) instead of
@@ -248,16 +288,12 @@ class InterSO3ConvFn(torch.autograd.Function):
                 grouped = torch.empty((d.b * d.p2 * d.na, d.ks), dtype=torch.float32, device=f.device)
             import contextlib
             with (_lib.kernel_policy(2) if ab("EPN_C1_MFMA") == "0" else contextlib.nullcontext()):   # A/B: the VALU kernel
-                _lib.check(_launch("inter_fwd", _inter_key(d), _inter_flops(d), f.device,
-                                   lambda: lib.epn_inter_so3conv_fwd_c1_f32(ctypes.byref(d), _cl_ptr(f), _lib.dev_ptr(Wc, "W"),
-                                                                            _cl_ptr(out), grouped.data_ptr() if grouped is not None
-                                                                            else None, wsp, wsn, _lib.stream_of(f))),
-                           "inter_so3conv_fwd_c1")
+                _run(rec, "inter_so3conv_fwd_c1", lib.epn_inter_so3conv_fwd_c1_f32, ctypes.byref(d), _cl_ptr(f),
+                     _lib.dev_ptr(Wc, "W"), _cl_ptr(out), grouped.data_ptr() if grouped is not None else None, wsp, wsn,
+                     _lib.stream_of(f))
         else:
-            _lib.check(_launch("inter_fwd", _inter_key(d), _inter_flops(d), f.device,
-                               lambda: lib.epn_inter_so3conv_fwd_f32(ctypes.byref(d), _cl_ptr(f), _lib.dev_ptr(Wc, "W"),
-                                                                     _cl_ptr(out), wsp, wsn, _lib.stream_of(f))),
-                       "inter_so3conv_fwd")
+            _run(rec, "inter_so3conv_fwd", lib.epn_inter_so3conv_fwd_f32, ctypes.byref(d), _cl_ptr(f), _lib.dev_ptr(Wc, "W"),
+                 _cl_ptr(out), wsp, wsn, _lib.stream_of(f))
         # (the saved grouped values go through save_for_backward like any saved activation: saved-tensor hooks, version
         # checks, release with the graph -- advisor finding, round 4)
         if grouped is not None:
@@ -279,15 +315,10 @@ class InterSO3ConvFn(torch.autograd.Function):
         cout = Wc.shape[0]
         cin = f.shape[1]
         d = geo.desc(cin, cout)
-        ws, wsp, wsn = _workspace(lib, d, f.device)
+        ws, wsp, wsn = _ws(lib.epn_inter_workspace_bytes(ctypes.byref(d)), f.device)
         gf = gW = None
         if ctx.needs_input_grad[0]:
-            gf = empty_cl(d.b, cin, d.p1, d.na, f.device)
-            _lib.check(_launch("inter_bwd_data", _inter_key(d), _inter_flops(d), f.device,
-                               lambda: lib.epn_inter_so3conv_bwd_data_f32(ctypes.byref(d), _cl_ptr(g),
-                                                                          _lib.dev_ptr(Wc, "W"), _cl_ptr(gf), wsp,
-                                                                          wsn, _lib.stream_of(f))),
-                       "inter_so3conv_bwd_data")
+            gf = _fused_bwd_data(lib, d, g, Wc, wsp, wsn)
         if ctx.needs_input_grad[1] and grouped is not None:
             gW = torch.empty_like(Wc)
             fl = 2.0 * d.b * d.p2 * d.na * cout * d.ks
@@ -309,25 +340,16 @@ class InterSO3ConvFn(torch.autograd.Function):
                         lambda: gemm.gemm_tn(g.permute(0, 2, 3, 1).reshape(-1, cout), grouped, out=gW, x_amax=xa, y_amax=ya,
                                              fp32_mode=form))
             else:
-                _lib.check(_launch("inter_bwd_weight_c1", _inter_key(d), fl, f.device,
-                                   lambda: lib.epn_inter_so3conv_bwd_weight_c1_f32(ctypes.byref(d), grouped.data_ptr(),
-                                                                                   _cl_ptr(g), _lib.dev_ptr(gW, "grad_W"),
-                                                                                   _lib.stream_of(f))),
-                           "inter_so3conv_bwd_weight_c1")
+                _run(("inter_bwd_weight_c1", _inter_key(d), fl, f.device), "inter_so3conv_bwd_weight_c1",
+                     lib.epn_inter_so3conv_bwd_weight_c1_f32, ctypes.byref(d), grouped.data_ptr(), _cl_ptr(g),
+                     _lib.dev_ptr(gW, "grad_W"), _lib.stream_of(f))
         elif ctx.needs_input_grad[1]:
-            gW = torch.empty_like(Wc)
-            _lib.check(_launch("inter_bwd_weight", _inter_key(d), _inter_flops(d), f.device,
-                               lambda: lib.epn_inter_so3conv_bwd_weight_f32(ctypes.byref(d), _cl_ptr(f), _cl_ptr(g),
-                                                                            _lib.dev_ptr(gW, "grad_W"), wsp, wsn,
-                                                                            _lib.stream_of(f))),
-                       "inter_so3conv_bwd_weight")
+            gW = _fused_bwd_weight(lib, d, f, g, Wc, wsp, wsn)
         return gf, gW, None
 
 
 def _group_workspace(lib, d, device):
-    nbytes = lib.epn_inter_group_workspace_bytes(ctypes.byref(d))
-    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
-    return ws, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())
+    return _ws(lib.epn_inter_group_workspace_bytes(ctypes.byref(d)), device)
 
 
 class InterGroupFn(torch.autograd.Function):
@@ -397,19 +419,15 @@ class InterSO3ConvSplitFn(torch.autograd.Function):
         cout, ck = Wc.shape
         cin = f.shape[1]
         d = geo.desc(cin, cout)
-        if ck != cin * d.ks or f.shape[2] != d.p1 or f.shape[3] != d.na or f.shape[0] != d.b:
-            raise ValueError(f"shape mismatch: feats {tuple(f.shape)}, W {tuple(Wc.shape)}, geometry "
-                             f"b={d.b} p1={d.p1} na={d.na} ks={d.ks}")
+        _check_inter_shapes(f, Wc, d)
         cols = d.b * d.p2 * d.na
         G = torch.empty((cols, ck), dtype=f.dtype, device=f.device)
         ws, wsp, wsn = _group_workspace(lib, d, f.device)
-        gflops = 9.0 * cols * d.ks * d.nn + 2.0 * cols * cin * d.ks * d.nn
         # packed column order of G (contiguous stores in the grouping kernel, include/epn_so3conv.h): W's columns follow
         packed = group_packed() and Wc.dtype == torch.float32 and bool(lib.epn_inter_group_packed_ok(ctypes.byref(d)))
-        grp = _entry(lib, "inter_group_packed" if packed else "inter_group", f.dtype)
-        _lib.check(_launch("inter_group", _inter_key(d), gflops, f.device,
-                           lambda: grp(ctypes.byref(d), _cl_ptr(f), ctypes.c_void_p(G.data_ptr()), wsp, wsn,
-                                       _lib.stream_of(f))), "inter_group")
+        _run(("inter_group", _inter_key(d), _group_flops(d), f.device), "inter_group",
+             _entry(lib, "inter_group_packed" if packed else "inter_group", f.dtype), ctypes.byref(d), _cl_ptr(f),
+             ctypes.c_void_p(G.data_ptr()), wsp, wsn, _lib.stream_of(f))
         if packed:
             Wd = torch.empty((cout, ck), dtype=f.dtype, device=f.device)
             _lib.check(_entry(lib, "inter_pack_weights", f.dtype)(_lib.dev_ptr(Wc, "W"), cout, cin, d.ks, Wd.data_ptr(),
@@ -421,24 +439,19 @@ class InterSO3ConvSplitFn(torch.autograd.Function):
         # 24 x smaller feature tensor -- an over-estimated maximum only narrows the window of full relative precision from
         # 2^17 to 2^17 / K below the true maximum (tests/test_gpu_bf16.py::test_f16x2_gemm_has_fp32_accuracy pins 64 x)
         g_amax = gemm.absmax_cached(f) * float(d.nn) if gemm.f16x2_on(G) else None
+        out2d = _launch("inter_gemm", _inter_key(d), 2.0 * cols * cout * ck, f.device,
+                        lambda: gemm.gemm_nt(G, Wd, col_stats=bool(share_input), a_amax=g_amax))
         if share_input:        # a block asks: its norm follows -- per-channel statistics from the GEMM's epilogue
-            out2d, part = _launch("inter_gemm", _inter_key(d), 2.0 * cols * cout * ck, f.device,
-                                  lambda: gemm.gemm_nt(G, Wd, col_stats=True, a_amax=g_amax))
+            out2d, part = out2d
             part = part if part is not None else torch.empty(0, dtype=torch.float32, device=f.device)
-        else:
-            out2d = _launch("inter_gemm", _inter_key(d), 2.0 * cols * cout * ck, f.device,
-                            lambda: gemm.gemm_nt(G, Wd, a_amax=g_amax))
         ctx.g_amax = g_amax
         ctx.save_for_backward(G, Wc)
         ctx.geo, ctx.cin, ctx.packed = geo, cin, packed
         out = out2d.view(d.b, d.p2, d.na, cout).permute(0, 3, 1, 2)
-        if share_input == "stats":
-            ctx.mark_non_differentiable(part)
-            return out, part
-        if share_input:
-            ctx.mark_non_differentiable(part)
-            return out, feats, part
-        return out
+        if not share_input:
+            return out
+        ctx.mark_non_differentiable(part)
+        return (out, part) if share_input == "stats" else (out, feats, part)
 
     # Tensor handles alive on a gradient that ONLY this backward can see: the engine's argument list + the Python wrapper.
     # A consumer whose backward hands ONE tensor to two inputs (`shared + other`) leaves a third handle in the other input's
@@ -514,147 +527,27 @@ class InterSO3ConvSplitFn(torch.autograd.Function):
     def backward(ctx, grad_out, grad_shared=None, _grad_part=None):
         if ctx.share_input == "stats":
             grad_shared = None
-        lib = _lib.get_lib()
-        G, Wc = ctx.saved_tensors
-        geo, cin = ctx.geo, ctx.cin
-        cout, ck = Wc.shape
-        d = geo.desc(cin, cout)
-        cols = d.b * d.p2 * d.na
-        if grad_out is None:                   # only the shared input was used downstream
-            return (grad_shared if ctx.needs_input_grad[0] else None), None, None, None
-        g = cast_feats(to_cl(grad_out, "grad_out"), G.dtype)
-        g2d = g.permute(0, 2, 3, 1).reshape(cols, cout)   # view of the channels-last buffer
         need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gemm_fl = 2.0 * cols * cout * ck
-        gf = gW = None
-        # two-piece fp16 contractions: max|dOut| once for both GEMMs it feeds (a pass over the narrow operand), max|G| as the
-        # forward pass bounded it
-        go_amax = gemm.absmax_cached(g) if gemm.f16x2_on(G) else None      # (tagged by the norm backward that produced it)
-        if need_w:
-            gW = _launch("inter_gemm_dw", _inter_key(d), gemm_fl, G.device,
-                         lambda: gemm.gemm_tn(g2d, G, x_amax=go_amax, y_amax=ctx.g_amax))
-            if ctx.packed:                                           # computed against packed G: columns back in c*ks + k order
-                gWp, gW = gW, torch.empty_like(gW)
-                _lib.check(lib.epn_inter_unpack_weight_grad_f32(gWp.data_ptr(), cout, cin, d.ks, gW.data_ptr(),
-                                                                _lib.stream_of(G)), "inter_unpack_weight_grad")
+        if grad_out is None:                   # only the shared input was used downstream
+            return (grad_shared if need_f else None), None, None, None
+        s = _split_bwd_operands(ctx, grad_out)
+        gW = _split_bwd_weight(s, ctx) if need_w else None
+        gf = None
         if need_f:
-            mode = os.environ.get("EPN_INTER_BWD_DATA", "auto")
-            if mode in ("auto", "cloud") and _ungroup_cloud_takes(lib, d, geo, G.dtype, mode):
-                # dG GEMM (its epilogue leaves max|dG|) + the transpose of the grouping with the cloud's gradient rows resident
-                # in LDS (csrc/inter_ungroup_cloud.hip: 64-bit fixed-point accumulators, no global atomics): no zero fill of a
-                # scatter target, the gradient is written in its own dtype, the other branch's gradient of a shared input is
-                # folded into the write-out, and the result is bitwise repeatable (so this is also the deterministic form)
-                Wt = gemm.transpose_cast(Wc, G.dtype)
-                dG, dg_amax = _launch("inter_gemm_dg", _inter_key(d), gemm_fl, G.device,
-                                      lambda: gemm.gemm_nt(g2d, Wt, a_amax=go_amax, c_amax=True))
-                add = None
-                if grad_shared is not None:
-                    add = cast_feats(to_cl(grad_shared, "grad_shared"), G.dtype)
-                gf = empty_cl(d.b, cin, d.p1, d.na, G.device, G.dtype)
-                nb = int(lib.epn_inter_ungroup_cloud_workspace_bytes(ctypes.byref(d)))
-                ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=G.device)
-                gflops = 9.0 * cols * d.ks * d.nn + 2.0 * cols * cin * d.ks * d.nn
-                args = [ctypes.byref(d), ctypes.c_void_p(dG.data_ptr()), gemm._use_amax(dg_amax), _cl_ptr(gf),
-                        None if add is None else _cl_ptr(add)]
-                if G.dtype == torch.bfloat16:
-                    args.append(0)                       # out_f32 = 0: the gradient leaves in bf16
-                fn = _entry(lib, "inter_ungroup_cloud", G.dtype)
-                _lib.check(_launch("inter_ungroup", _inter_key(d), gflops, G.device,
-                                   lambda: fn(*args, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
-                                              _lib.stream_of(G))), "inter_ungroup_cloud")
-                return gf, gW, None, None
-            if mode == "cloud":
-                mode = "split"
-            # the other branch's gradient of the shared input: fp32 -> the scatter accumulates onto it; otherwise added below
-            # (bf16 features: starting the fp32 scatter target from the converted gradient instead of zeros measured no gain --
-            # 1444 vs 1455 point-clouds/s on the rotation network -- so that path keeps the plain addition)
-            onto = (grad_shared is not None and grad_shared.dtype == torch.float32 and G.dtype == torch.float32
-                    and mode != "fused" and not deterministic_bwd(G.dtype)
-                    and InterSO3ConvSplitFn._may_write_into(ctx, grad_shared))
-            if onto:
-                # the scatter writes this tensor through its raw pointer: bump its version so that no maximum remembered on
-                # it (or on a view / alias of it) survives the write (gemm.mark_written)
-                gf, grad_shared = gemm.mark_written(to_cl(grad_shared, "grad_shared").detach()), None
-            else:
-                gf = empty_cl(d.b, cin, d.p1, d.na, G.device)       # fp32: the scatter target of either dtype
-            if G.dtype != torch.float32 or deterministic_bwd(G.dtype):
-                mode = "split"          # bf16 features / deterministic mode: dG GEMM + (atomic-free) transpose of the grouping
-            elif mode == "auto":
-                # Three forms.  Measured per layer of the ModelNet schedule at B = 32 (ms; pair = dG GEMM + LDS-pre-reduced
-                # transpose | on-chip kernel, csrc/inter_bwd_f2.hip: dG never written):
-                #   stand-alone (tools/bwd_onchip_probe.py, profiles/r06_bwd_onchip_probe.txt)
-                #     K = 16:  64->64 3.09 | 2.50   128->128 3.40 | 2.94   256->256 4.56 | 4.26
-                #     K = 32:  64->128 2.17 | 2.80  128->256 2.52 | 3.24   256->256 2.58 | 3.16
-                #   inside the training step (bench per_call, one box): K = 16: 2.75 | 2.72, 3.38 | 3.33, 4.39 | 4.81 -- the pair is
-                #   HBM-bound and keeps its speed on a chip at its power limit, the on-chip kernel is latency-bound and does not;
-                #   the step: 536-537 point-clouds/s (pair everywhere) vs 530-532 (on-chip at K = 16) vs 505-510 (on-chip everywhere).
-                # So the pair stays the default; EPN_INTER_BWD_DATA=onchip is the form that moves 36-54 GB less per step and
-                # allocates no [cols, cin*ks] gradient; round 1's fused exact-f32 kernel (=fused) writes no such tensor either.
-                mode = "split"
-            if (mode == "onchip" and gemm.f16x2_on(G) and go_amax is not None and isinstance(geo, InterGeometry)
-                    and lib.epn_inter_bwd_data_f16x2_ok(ctypes.byref(d))):
-                # dG never written (csrc/inter_bwd_f2.hip): the two-piece contraction dOut . W runs inside the workgroup of the
-                # LDS-reduced scatter, its D fragments reach the tail through in-register row transposes
-                nb = int(lib.epn_inter_bwd_data_f16x2_workspace_bytes(ctypes.byref(d)))
-                ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=G.device)
-                gemm._check_amax(g2d, go_amax, "inter_bwd_data_f16x2, operand dOut")
-                _lib.check(_launch("inter_bwd_data_f2", _inter_key(d), _inter_flops(d), G.device,
-                                   lambda: lib.epn_inter_bwd_data_f16x2_f32(ctypes.byref(d), _cl_ptr(g), _lib.dev_ptr(Wc, "W"),
-                                                                            gemm._use_amax(go_amax), _cl_ptr(gf), 1 if onto else 0,
-                                                                            ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
-                                                                            _lib.stream_of(G))), "inter_bwd_data_f16x2")
-            elif mode == "fused" and lib.epn_inter_is_fused(ctypes.byref(d)) and cin >= 16:
-                # The fused data-gradient kernel (W^T dOut + per-column tail in one pass, no dG tensor): its fp32 atomic
-                # scatter -- cols*K*cin = 1.0e9 atomics per layer -- hides under the MFMA phases.  Also measured and
-                # dropped: an atomic-free CSR-gather transpose (re-reads every 96-byte dG row K times: 3x slower) and
-                # running the weight-gradient GEMM on a side stream underneath the scatter (no overlap: +-1 ms).
-                ws, wsp, wsn = _workspace(lib, d, G.device)
-                _lib.check(_launch("inter_bwd_data", _inter_key(d), _inter_flops(d), G.device,
-                                   lambda: lib.epn_inter_so3conv_bwd_data_f32(ctypes.byref(d), _cl_ptr(g),
-                                                                              _lib.dev_ptr(Wc, "W"), _cl_ptr(gf), wsp,
-                                                                              wsn, _lib.stream_of(G))),
-                           "inter_so3conv_bwd_data")
-            else:
-                Wt = gemm.transpose_cast(Wc, G.dtype)                        # [ck, cout]: dG = dOut W as an NT GEMM
-                dG = _launch("inter_gemm_dg", _inter_key(d), gemm_fl, G.device, lambda: gemm.gemm_nt(g2d, Wt, a_amax=go_amax))
-                ws, wsp, wsn = _group_workspace(lib, d, G.device)
-                gflops = 9.0 * cols * d.ks * d.nn + 2.0 * cols * cin * d.ks * d.nn
-                if deterministic_bwd(G.dtype) and isinstance(geo, InterGeometry) and d.na >= 16:
-                    # atomic-free: per-slot slab + ordered reduction over the inverse neighbour list (bitwise repeatable;
-                    # for bf16 also faster than the fp32 atomic scatter + conversion at K >= 32)
-                    off, ent = geo.inverse_list()
-                    gf = empty_cl(d.b, cin, d.p1, d.na, G.device, G.dtype)
-                    # + one byte per (point, neighbour slot) behind the slab: marks of the pre-reduced form
-                    extra = (d.b * d.p2 * d.nn + 512 + G.element_size() - 1) // G.element_size()
-                    slab = torch.empty(d.b * d.p2 * d.nn * d.na * cin + extra, dtype=G.dtype, device=G.device)
-                    det = _entry(lib, "inter_ungroup_det", G.dtype)
-                    _lib.check(_launch("inter_ungroup_det", _inter_key(d), gflops, G.device,
-                                       lambda: det(ctypes.byref(d), ctypes.c_void_p(dG.data_ptr()), _cl_ptr(gf),
-                                                   _lib.dev_ptr(off, "offsets", torch.int32),
-                                                   _lib.dev_ptr(ent, "entries", torch.int32),
-                                                   ctypes.c_void_p(slab.data_ptr()), slab.numel() * slab.element_size(),
-                                                   wsp, wsn, _lib.stream_of(G))), "inter_ungroup_det")
-                    if grad_shared is not None:
-                        gf = gf + grad_shared.to(gf.dtype)
-                    return gf, gW, None, None
-                ungrp = _entry(lib, "inter_ungroup_acc" if onto else "inter_ungroup", G.dtype)
-                _lib.check(_launch("inter_ungroup", _inter_key(d), gflops, G.device,
-                                   lambda: ungrp(ctypes.byref(d), ctypes.c_void_p(dG.data_ptr()), _cl_ptr(gf), wsp, wsn,
-                                                 _lib.stream_of(G))), "inter_ungroup")
-            if (grad_shared is not None and G.dtype == torch.bfloat16 and gf.dtype == torch.float32
-                    and grad_shared.dtype == torch.bfloat16):
-                gs = to_cl(grad_shared, "grad_shared")           # bf16(gf) + the other branch's gradient in one pass
-                out = empty_cl(d.b, cin, d.p1, d.na, G.device, torch.bfloat16)
-                _lib.check(lib.epn_cast_add_bf16(gf.data_ptr(), gs.data_ptr(), out.data_ptr(), gf.numel(), _lib.stream_of(gf)),
-                           "cast_add")
-                return out, gW, None, None
-            gf = cast_feats(gf, G.dtype)
-            if grad_shared is not None:
-                gf = gf + grad_shared.to(gf.dtype)
+            lib, dp = s.lib, ctypes.byref(s.d)
+            form, onto = select_inter_bwd_data(
+                s.G.dtype, s.d.nn, s.d.cin, s.d.na, isinstance(s.geo, InterGeometry), os.environ.get("EPN_INTER_BWD_DATA", "auto"),
+                deterministic_bwd(s.G.dtype), gemm.f16x2_on(s.G) and s.go_amax is not None,
+                cloud_ok=lambda: lib.epn_inter_ungroup_cloud_ok(dp), onchip_ok=lambda: lib.epn_inter_bwd_data_f16x2_ok(dp),
+                fused_ok=lambda: lib.epn_inter_is_fused(dp),
+                may_write=lambda: (grad_shared is not None and grad_shared.dtype == torch.float32
+                                   and InterSO3ConvSplitFn._may_write_into(ctx, grad_shared)))
+            gf, folded = _INTER_BWD_DATA[form](s, grad_shared, onto)
+            gf = _fold_grad_shared(gf, None if folded else grad_shared, s.G.dtype)
         return gf, gW, None, None
 
 
-def _ungroup_cloud_takes(lib, d, geo, dtype, mode):
+def _ungroup_cloud_takes(lazy_geo, cloud_ok, dtype, nn, mode, deterministic):
     """Does the cloud-resident transpose of the grouping (epn_inter_ungroup_cloud_*) take this layer?  mode "cloud": whenever
     the kernel can; "auto": where it is measured faster INSIDE the training step than the LDS-pre-reduced atomic scatter
     (profiles/r06_ab_ungroup_cloud.txt, A/B on one box) -- bf16 features: rotation network 1957-1966 -> 2095-2115
@@ -662,51 +555,209 @@ def _ungroup_cloud_takes(lib, d, geo, dtype, mode):
     features up to K = 32: cls 530-532 -> 537-538 (until its table kernel was fixed -- 91 -> 20 us per call -- this was a tie);
     fp32 at K = 64 regenerates its weights per 16 channels under the register cap and loses (rotation network in fp32 with the
     form everywhere: 1033 -> 1004) -- and always in deterministic mode, which it satisfies by construction (the slab-based
-    kernels cost 3.6-8 % of a step)."""
-    if not isinstance(geo, InterGeometry) or not lib.epn_inter_ungroup_cloud_ok(ctypes.byref(d)):
+    kernels cost 3.6-8 % of a step).  lazy_geo: an InterGeometry (not dense inter_w); cloud_ok(): the library's predicate."""
+    if not lazy_geo or not cloud_ok():
         return False
-    if mode == "cloud" or deterministic_bwd(dtype):
+    if mode == "cloud" or deterministic:
         return True
-    return dtype == torch.bfloat16 or d.nn <= 32
+    return dtype == torch.bfloat16 or nn <= 32
 
 
-def _lib_generic():
-    return False      # the generic-kernel policy is only ever set by the cross-check tests, around whole calls
+def select_inter_bwd_data(dtype, nn, cin, na, lazy_geo, mode, deterministic, f16x2, cloud_ok, onchip_ok, fused_ok, may_write):
+    """Which form does the data gradient of the split InterSO3Conv take?  -> (form, onto): a key of _INTER_BWD_DATA, and
+    whether it accumulates in place onto the incoming gradient of a shared input (scatter and onchip only).
+    dtype: of the grouped features; nn = K; lazy_geo: an InterGeometry (not dense inter_w); mode: EPN_INTER_BWD_DATA = auto
+    (default) | cloud | split | onchip | fused; deterministic: EPN_DETERMINISTIC; f16x2: two-piece fp16 contractions with
+    max|dOut| at hand.  cloud_ok / onchip_ok / fused_ok: the library's predicates for the layer; may_write: a gradient of a
+    shared input is there, fp32, and nobody else can see it -- each is called only where a rule needs it.
+    Three fp32 forms were measured per layer of the ModelNet schedule at B = 32 (ms; pair = dG GEMM + LDS-pre-reduced
+    transpose | on-chip kernel, csrc/inter_bwd_f2.hip: dG never written):
+      stand-alone (tools/bwd_onchip_probe.py, profiles/r06_bwd_onchip_probe.txt)
+        K = 16:  64->64 3.09 | 2.50   128->128 3.40 | 2.94   256->256 4.56 | 4.26
+        K = 32:  64->128 2.17 | 2.80  128->256 2.52 | 3.24   256->256 2.58 | 3.16
+      inside the training step (bench per_call, one box): K = 16: 2.75 | 2.72, 3.38 | 3.33, 4.39 | 4.81 -- the pair is
+      HBM-bound and keeps its speed on a chip at its power limit, the on-chip kernel is latency-bound and does not;
+      the step: 536-537 point-clouds/s (pair everywhere) vs 530-532 (on-chip at K = 16) vs 505-510 (on-chip everywhere).
+    So the pair stays what auto takes; EPN_INTER_BWD_DATA=onchip is the form that moves 36-54 GB less per step and
+    allocates no [cols, cin*ks] gradient; round 1's fused exact-f32 kernel (=fused) writes no such tensor either."""
+    if mode in ("auto", "cloud") and _ungroup_cloud_takes(lazy_geo, cloud_ok, dtype, nn, mode, deterministic):
+        return "cloud", False
+    f32 = dtype == torch.float32
+    if not f32 or deterministic or mode not in ("onchip", "fused"):
+        mode = "split"          # bf16 features / deterministic mode: dG GEMM + (atomic-free) transpose of the grouping
+    # the other branch's gradient of the shared input: fp32 -> the scatter accumulates onto it; otherwise added afterwards
+    # (bf16 features: starting the fp32 scatter target from the converted gradient instead of zeros measured no gain --
+    # 1444 vs 1455 point-clouds/s on the rotation network -- so that path keeps the plain addition)
+    onto = f32 and not deterministic and mode != "fused" and may_write()
+    if mode == "onchip" and f16x2 and lazy_geo and onchip_ok():
+        return "onchip", onto
+    if mode == "fused" and fused_ok() and cin >= 16:
+        return "fused", False
+    if deterministic and lazy_geo and na >= 16:
+        return "slab", False
+    return "scatter", onto
 
 
-def _onchip_workspace(lib, d, bf16, device):
-    nbytes = lib.epn_inter_onchip_workspace_bytes(ctypes.byref(d), int(bf16))
-    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
-    return ws, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())
+def _split_bwd_operands(ctx, grad_out):
+    """What the weight gradient and every data-gradient form of one backward call start from."""
+    G, Wc = ctx.saved_tensors
+    cout, ck = Wc.shape
+    d = ctx.geo.desc(ctx.cin, cout)
+    cols = d.b * d.p2 * d.na
+    g = cast_feats(to_cl(grad_out, "grad_out"), G.dtype)
+    # two-piece fp16 contractions: max|dOut| once for both GEMMs it feeds (a pass over the narrow operand), max|G| as the
+    # forward pass bounded it
+    go_amax = gemm.absmax_cached(g) if gemm.f16x2_on(G) else None      # (tagged by the norm backward that produced it)
+    return types.SimpleNamespace(lib=_lib.get_lib(), geo=ctx.geo, d=d, G=G, Wc=Wc, g=g, go_amax=go_amax,
+                                 g2d=g.permute(0, 2, 3, 1).reshape(cols, cout),   # view of the channels-last buffer
+                                 gemm_fl=2.0 * cols * cout * ck)
+
+
+def _split_bwd_weight(s, ctx):
+    d, G = s.d, s.G
+    gW = _launch("inter_gemm_dw", _inter_key(d), s.gemm_fl, G.device,
+                 lambda: gemm.gemm_tn(s.g2d, G, x_amax=s.go_amax, y_amax=ctx.g_amax))
+    if ctx.packed:                                           # computed against packed G: columns back in c*ks + k order
+        gWp, gW = gW, torch.empty_like(gW)
+        _lib.check(s.lib.epn_inter_unpack_weight_grad_f32(gWp.data_ptr(), gW.shape[0], d.cin, d.ks, gW.data_ptr(),
+                                                          _lib.stream_of(G)), "inter_unpack_weight_grad")
+    return gW
+
+
+def _dg_gemm(s, **kw):
+    Wt = gemm.transpose_cast(s.Wc, s.G.dtype)                        # [ck, cout]: dG = dOut W as an NT GEMM
+    return _launch("inter_gemm_dg", _inter_key(s.d), s.gemm_fl, s.G.device,
+                   lambda: gemm.gemm_nt(s.g2d, Wt, a_amax=s.go_amax, **kw))
+
+
+def _scatter_target(s, grad_shared, onto):
+    if onto:
+        # the scatter writes this tensor through its raw pointer: bump its version so that no maximum remembered on
+        # it (or on a view / alias of it) survives the write (gemm.mark_written)
+        return gemm.mark_written(to_cl(grad_shared, "grad_shared").detach())
+    return empty_cl(s.d.b, s.d.cin, s.d.p1, s.d.na, s.G.device)       # fp32: the scatter target of either dtype
+
+
+def _bwd_data_cloud(s, grad_shared, onto):
+    """dG GEMM (its epilogue leaves max|dG|) + the transpose of the grouping with the cloud's gradient rows resident in LDS
+    (csrc/inter_ungroup_cloud.hip: 64-bit fixed-point accumulators, no global atomics): no zero fill of a scatter target,
+    the gradient is written in its own dtype, the other branch's gradient of a shared input is folded into the write-out,
+    and the result is bitwise repeatable (so this is also the deterministic form)."""
+    lib, d, G = s.lib, s.d, s.G
+    dG, dg_amax = _dg_gemm(s, c_amax=True)
+    add = None if grad_shared is None else cast_feats(to_cl(grad_shared, "grad_shared"), G.dtype)
+    gf = empty_cl(d.b, d.cin, d.p1, d.na, G.device, G.dtype)
+    ws, wsp, wsn = _ws(lib.epn_inter_ungroup_cloud_workspace_bytes(ctypes.byref(d)), G.device)
+    args = [ctypes.byref(d), ctypes.c_void_p(dG.data_ptr()), gemm._use_amax(dg_amax), _cl_ptr(gf),
+            None if add is None else _cl_ptr(add)]
+    if G.dtype == torch.bfloat16:
+        args.append(0)                       # out_f32 = 0: the gradient leaves in bf16
+    _run(("inter_ungroup", _inter_key(d), _group_flops(d), G.device), "inter_ungroup_cloud",
+         _entry(lib, "inter_ungroup_cloud", G.dtype), *args, wsp, wsn, _lib.stream_of(G))
+    return gf, True
+
+
+def _bwd_data_onchip(s, grad_shared, onto):
+    """dG never written (csrc/inter_bwd_f2.hip): the two-piece contraction dOut . W runs inside the workgroup of the
+    LDS-reduced scatter, its D fragments reach the tail through in-register row transposes."""
+    lib, d, G = s.lib, s.d, s.G
+    gf = _scatter_target(s, grad_shared, onto)
+    ws, wsp, wsn = _ws(lib.epn_inter_bwd_data_f16x2_workspace_bytes(ctypes.byref(d)), G.device)
+    gemm._check_amax(s.g2d, s.go_amax, "inter_bwd_data_f16x2, operand dOut")
+    _run(("inter_bwd_data_f2", _inter_key(d), _inter_flops(d), G.device), "inter_bwd_data_f16x2",
+         lib.epn_inter_bwd_data_f16x2_f32, ctypes.byref(d), _cl_ptr(s.g), _lib.dev_ptr(s.Wc, "W"), gemm._use_amax(s.go_amax),
+         _cl_ptr(gf), 1 if onto else 0, wsp, wsn, _lib.stream_of(G))
+    return gf, onto
+
+
+def _bwd_data_fused(s, grad_shared, onto):
+    """The fused data-gradient kernel (W^T dOut + per-column tail in one pass, no dG tensor): its fp32 atomic scatter --
+    cols*K*cin = 1.0e9 atomics per layer -- hides under the MFMA phases.  Also measured and dropped: an atomic-free
+    CSR-gather transpose (re-reads every 96-byte dG row K times: 3x slower) and running the weight-gradient GEMM on a side
+    stream underneath the scatter (no overlap: +-1 ms)."""
+    ws, wsp, wsn = _ws(s.lib.epn_inter_workspace_bytes(ctypes.byref(s.d)), s.G.device)
+    return _fused_bwd_data(s.lib, s.d, s.g, s.Wc, wsp, wsn), False
+
+
+def _bwd_data_slab(s, grad_shared, onto):
+    """dG GEMM + the atomic-free transpose: per-slot slab + ordered reduction over the inverse neighbour list (bitwise
+    repeatable; for bf16 also faster than the fp32 atomic scatter + conversion at K >= 32)."""
+    lib, d, G = s.lib, s.d, s.G
+    dG = _dg_gemm(s)
+    ws, wsp, wsn = _group_workspace(lib, d, G.device)
+    off, ent = s.geo.inverse_list()
+    gf = empty_cl(d.b, d.cin, d.p1, d.na, G.device, G.dtype)
+    # + one byte per (point, neighbour slot) behind the slab: marks of the pre-reduced form
+    extra = (d.b * d.p2 * d.nn + 512 + G.element_size() - 1) // G.element_size()
+    slab = torch.empty(d.b * d.p2 * d.nn * d.na * d.cin + extra, dtype=G.dtype, device=G.device)
+    _run(("inter_ungroup_det", _inter_key(d), _group_flops(d), G.device), "inter_ungroup_det",
+         _entry(lib, "inter_ungroup_det", G.dtype), ctypes.byref(d), ctypes.c_void_p(dG.data_ptr()), _cl_ptr(gf),
+         _lib.dev_ptr(off, "offsets", torch.int32), _lib.dev_ptr(ent, "entries", torch.int32),
+         ctypes.c_void_p(slab.data_ptr()), slab.numel() * slab.element_size(), wsp, wsn, _lib.stream_of(G))
+    return gf, False
+
+
+def _bwd_data_scatter(s, grad_shared, onto):
+    """dG GEMM + the LDS-pre-reduced atomic transpose of the grouping, into a fresh fp32 tensor or (onto) the shared gradient."""
+    lib, d, G = s.lib, s.d, s.G
+    gf = _scatter_target(s, grad_shared, onto)
+    dG = _dg_gemm(s)
+    ws, wsp, wsn = _group_workspace(lib, d, G.device)
+    _run(("inter_ungroup", _inter_key(d), _group_flops(d), G.device), "inter_ungroup",
+         _entry(lib, "inter_ungroup_acc" if onto else "inter_ungroup", G.dtype), ctypes.byref(d),
+         ctypes.c_void_p(dG.data_ptr()), _cl_ptr(gf), wsp, wsn, _lib.stream_of(G))
+    return gf, onto
+
+
+# form -> f(s, grad_shared, onto) -> (gradient, "it already contains grad_shared")
+_INTER_BWD_DATA = {"cloud": _bwd_data_cloud, "onchip": _bwd_data_onchip, "fused": _bwd_data_fused, "slab": _bwd_data_slab,
+                   "scatter": _bwd_data_scatter}
+
+
+def _fold_grad_shared(gf, grad_shared, dtype):
+    """gf in the features' dtype + the other branch's gradient of a shared input (None: none, or the form added it)."""
+    if grad_shared is None:
+        return cast_feats(gf, dtype)
+    if dtype == torch.bfloat16 and gf.dtype == torch.float32 and grad_shared.dtype == torch.bfloat16:
+        gs = to_cl(grad_shared, "grad_shared")           # bf16(gf) + the other branch's gradient in one pass
+        out = empty_cl(*gs.shape, gs.device, torch.bfloat16)
+        _lib.check(_lib.get_lib().epn_cast_add_bf16(gf.data_ptr(), gs.data_ptr(), out.data_ptr(), gf.numel(),
+                                                    _lib.stream_of(gf)), "cast_add")
+        return out
+    return cast_feats(gf, dtype) + grad_shared.to(dtype)
+
+
+def _onchip_lib_ok(feats, W, geo):
+    d = geo.desc(feats.shape[1], W.shape[0])
+    return _lib.get_lib().epn_inter_onchip_ok(ctypes.byref(d), int(feats.dtype == torch.bfloat16))
 
 
 def inter_onchip_ok(feats, W, geo):
     """Does the on-chip form (csrc/inter_fx.hip: grouping = A-tile producer of the weight contraction) take this layer?"""
-    if isinstance(geo, DenseInterWeights) or not feats.is_cuda or feats.dtype not in FEATURE_DTYPES:
+    return _onchip_takes(feats.dtype, isinstance(geo, DenseInterWeights), feats.is_cuda, gemm.FP32_MODE,
+                         lambda: _onchip_lib_ok(feats, W, geo))
+
+
+def _onchip_takes(dtype, dense, is_cuda, fp32_mode, lib_ok):
+    if dense or not is_cuda or dtype not in FEATURE_DTYPES:
         return False
-    if feats.dtype == torch.float32 and gemm.FP32_MODE == "native":
+    if dtype == torch.float32 and fp32_mode == "native":
         return False                      # the on-chip fp32 form IS a split (3 x bf16) contraction: not under the exact-f32 switch
-    d = geo.desc(feats.shape[1], W.shape[0])
-    return bool(_lib.get_lib().epn_inter_onchip_ok(ctypes.byref(d), int(feats.dtype == torch.bfloat16)))
+    return bool(lib_ok())
 
 
 def inter_onchip_fwd(f, Wc, geo):
     """out_cl [b, cout, p2, na] (channels-last) of InterSO3Conv with no [cols, cin*ks] tensor (epn_inter_so3conv_fwd_onchip_f32 /
     epn_inter_so3conv_fwd_bf16)."""
     lib = _lib.get_lib()
-    cout, ck = Wc.shape
-    cin = f.shape[1]
-    d = geo.desc(cin, cout)
-    if ck != cin * d.ks or f.shape[2] != d.p1 or f.shape[3] != d.na or f.shape[0] != d.b:
-        raise ValueError(f"shape mismatch: feats {tuple(f.shape)}, W {tuple(Wc.shape)}, geometry "
-                         f"b={d.b} p1={d.p1} na={d.na} ks={d.ks}")
+    d = geo.desc(f.shape[1], Wc.shape[0])
+    _check_inter_shapes(f, Wc, d)
     bf = f.dtype == torch.bfloat16
-    out = empty_cl(d.b, cout, d.p2, d.na, f.device, f.dtype)
-    ws, wsp, wsn = _onchip_workspace(lib, d, bf, f.device)
-    fn = lib.epn_inter_so3conv_fwd_bf16 if bf else lib.epn_inter_so3conv_fwd_onchip_f32
-    _lib.check(_launch("inter_fwd_onchip", _inter_key(d), _inter_flops(d), f.device,
-                       lambda: fn(ctypes.byref(d), _cl_ptr(f), _lib.dev_ptr(Wc, "W"), _cl_ptr(out), wsp, wsn,
-                                  _lib.stream_of(f))), "inter_so3conv_fwd_onchip")
+    out = empty_cl(d.b, d.cout, d.p2, d.na, f.device, f.dtype)
+    ws, wsp, wsn = _ws(lib.epn_inter_onchip_workspace_bytes(ctypes.byref(d), int(bf)), f.device)
+    _run(("inter_fwd_onchip", _inter_key(d), _inter_flops(d), f.device), "inter_so3conv_fwd_onchip",
+         lib.epn_inter_so3conv_fwd_bf16 if bf else lib.epn_inter_so3conv_fwd_onchip_f32, ctypes.byref(d), _cl_ptr(f),
+         _lib.dev_ptr(Wc, "W"), _cl_ptr(out), wsp, wsn, _lib.stream_of(f))
     return out
 
 
@@ -729,25 +780,13 @@ class InterSO3ConvOnChipFn(torch.autograd.Function):
         need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         lib = _lib.get_lib()
         d = geo.desc(f.shape[1], Wc.shape[0])
-        if f.dtype == torch.float32 and lib.epn_inter_is_fused(ctypes.byref(d)) and not _lib_generic():
+        if f.dtype == torch.float32 and lib.epn_inter_is_fused(ctypes.byref(d)):
             # fp32: the fused transposes of csrc/inter_mfma.hip (exact-f32 MFMAs; grouped features and their gradient stay
             # on chip there too) -- the whole layer then writes no [cols, cin*ks] tensor in either direction
             g = to_cl(grad_out, "grad_out")
-            ws, wsp, wsn = _workspace(lib, d, f.device)
-            gf = gW = None
-            if need_f:
-                gf = empty_cl(d.b, f.shape[1], d.p1, d.na, f.device)
-                _lib.check(_launch("inter_bwd_data", _inter_key(d), _inter_flops(d), f.device,
-                                   lambda: lib.epn_inter_so3conv_bwd_data_f32(ctypes.byref(d), _cl_ptr(g), _lib.dev_ptr(Wc, "W"),
-                                                                              _cl_ptr(gf), wsp, wsn, _lib.stream_of(f))),
-                           "inter_so3conv_bwd_data")
-            if need_w:
-                gW = torch.empty_like(Wc)
-                _lib.check(_launch("inter_bwd_weight", _inter_key(d), _inter_flops(d), f.device,
-                                   lambda: lib.epn_inter_so3conv_bwd_weight_f32(ctypes.byref(d), _cl_ptr(f), _cl_ptr(g),
-                                                                                _lib.dev_ptr(gW, "grad_W"), wsp, wsn,
-                                                                                _lib.stream_of(f))),
-                           "inter_so3conv_bwd_weight")
+            ws, wsp, wsn = _ws(lib.epn_inter_workspace_bytes(ctypes.byref(d)), f.device)
+            gf = _fused_bwd_data(lib, d, g, Wc, wsp, wsn) if need_f else None
+            gW = _fused_bwd_weight(lib, d, f, g, Wc, wsp, wsn) if need_w else None
             return gf, gW, None
         # bf16 features: transposes through the split form (grouped features recomputed, not saved)
         with torch.enable_grad():
@@ -785,7 +824,6 @@ class _TensorCache:
         self._d, self._maxlen = {}, maxlen
 
     def get(self, t, make):
-        import weakref
         k = id(t)
         e = self._d.get(k)
         if e is not None and e[0]() is t and e[1] == t._version:
@@ -818,12 +856,6 @@ def inverse_intra_idx(intra_idx32):
     return _INV_CACHE.get(intra_idx32, _make_inverse)
 
 
-def _intra_ws(lib, na, kn, cin, cout, device):
-    nbytes = lib.epn_intra_workspace_bytes(na, kn, cin, cout)
-    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
-    return ws, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())
-
-
 class IntraSO3ConvFn(torch.autograd.Function):
     """out[b,o,p,a] = sum_{c,k} W[o,c*kn+k] feats[b,c,p,intra_idx[a,k]]
     (IntraSO3Conv.forward, vgtk/vgtk/so3conv/modules.py:197-200), fused."""
@@ -836,17 +868,13 @@ class IntraSO3ConvFn(torch.autograd.Function):
         b, cin, p, na = f.shape
         cout = Wc.shape[0]
         kn = intra_idx32.shape[1]
-        if Wc.shape[1] != cin * kn or intra_idx32.shape[0] != na:
-            raise ValueError(f"shape mismatch: feats {tuple(f.shape)}, W {tuple(Wc.shape)}, "
-                             f"intra_idx {tuple(intra_idx32.shape)}")
+        _check_intra_shapes(f, Wc, intra_idx32)
         out = empty_cl(b, cout, p, na, f.device)
-        ws, wsp, wsn = _intra_ws(lib, na, kn, cin, cout, f.device)
+        ws, wsp, wsn = _ws(lib.epn_intra_workspace_bytes(na, kn, cin, cout), f.device)
         fl = 2.0 * b * p * na * cout * cin * kn
-        _lib.check(_launch("intra_fwd", (b, p, na, kn, cin, cout), fl, f.device,
-                           lambda: lib.epn_intra_so3conv_fwd_f32(
-                               _cl_ptr(f), _lib.dev_ptr(intra_idx32, "intra_idx", torch.int32), _lib.dev_ptr(Wc, "W"),
-                               b, p, na, kn, cin, cout, _cl_ptr(out), wsp, wsn, _lib.stream_of(f))),
-                   "intra_so3conv_fwd")
+        _run(("intra_fwd", (b, p, na, kn, cin, cout), fl, f.device), "intra_so3conv_fwd", lib.epn_intra_so3conv_fwd_f32,
+             _cl_ptr(f), _lib.dev_ptr(intra_idx32, "intra_idx", torch.int32), _lib.dev_ptr(Wc, "W"), b, p, na, kn, cin, cout,
+             _cl_ptr(out), wsp, wsn, _lib.stream_of(f))
         ctx.save_for_backward(f, Wc, intra_idx32)
         return out
 
@@ -858,35 +886,36 @@ class IntraSO3ConvFn(torch.autograd.Function):
         b, cin, p, na = f.shape
         cout = Wc.shape[0]
         kn = iidx.shape[1]
-        ip = _lib.dev_ptr(iidx, "intra_idx", torch.int32)
         fl = 2.0 * b * p * na * cout * cin * kn
         gf = gW = None
         if ctx.needs_input_grad[0]:
-            gf = empty_cl(b, cin, p, na, f.device)
-            inv = inverse_intra_idx(iidx)
-            ws, wsp, wsn = _intra_ws(lib, na, kn, cin, cout, f.device)
-            _lib.check(_launch("intra_bwd_data", (b, p, na, kn, cin, cout), fl, f.device,
-                               lambda: lib.epn_intra_so3conv_bwd_data_f32(
-                                   _cl_ptr(g), ip, _lib.dev_ptr(inv, "inv_idx", torch.int32), _lib.dev_ptr(Wc, "W"),
-                                   b, p, na, kn, cin, cout, _cl_ptr(gf), wsp, wsn, _lib.stream_of(f))),
-                       "intra_so3conv_bwd_data")
+            gf = _intra_fused_bwd_data(lib, g, iidx, inverse_intra_idx(iidx), Wc, cin)
         if ctx.needs_input_grad[1]:
             gW = torch.empty_like(Wc)
-            _lib.check(_launch("intra_bwd_weight", (b, p, na, kn, cin, cout), fl, f.device,
-                               lambda: lib.epn_intra_so3conv_bwd_weight_f32(
-                                   _cl_ptr(f), _cl_ptr(g), ip, b, p, na, kn, cin, cout, _lib.dev_ptr(gW, "grad_W"),
-                                   _lib.stream_of(f))),
-                       "intra_so3conv_bwd_weight")
+            _run(("intra_bwd_weight", (b, p, na, kn, cin, cout), fl, f.device), "intra_so3conv_bwd_weight",
+                 lib.epn_intra_so3conv_bwd_weight_f32, _cl_ptr(f), _cl_ptr(g), _lib.dev_ptr(iidx, "intra_idx", torch.int32),
+                 b, p, na, kn, cin, cout, _lib.dev_ptr(gW, "grad_W"), _lib.stream_of(f))
         return gf, gW, None
+
+
+def _intra_fused_bwd_data(lib, g, iidx, inv, Wc, cin):
+    """Data gradient of IntraSO3Conv on the fused fp32 kernel (no grouped-gradient tensor); g: fp32 channels-last."""
+    b, cout, p, na = g.shape
+    kn = iidx.shape[1]
+    gf = empty_cl(b, cin, p, na, g.device)
+    ws, wsp, wsn = _ws(lib.epn_intra_workspace_bytes(na, kn, cin, cout), g.device)
+    _run(("intra_bwd_data", (b, p, na, kn, cin, cout), 2.0 * b * p * na * cout * cin * kn, g.device), "intra_so3conv_bwd_data",
+         lib.epn_intra_so3conv_bwd_data_f32, _cl_ptr(g), _lib.dev_ptr(iidx, "intra_idx", torch.int32),
+         _lib.dev_ptr(inv, "inv_idx", torch.int32), _lib.dev_ptr(Wc, "W"), b, p, na, kn, cin, cout, _cl_ptr(gf), wsp, wsn,
+         _lib.stream_of(g))
+    return gf
 
 
 def _intra_group(lib, f, idx32, b, p, na, kn, c):
     """grouped[col][k*c + ci] = f[b][p][idx[a,k]][ci] (epn_intra_group_*), any feature dtype."""
     G = torch.empty((b * p * na, kn * c), dtype=f.dtype, device=f.device)
-    _lib.check(_launch("intra_group", (b, p, na, kn, c), 0.0, f.device,
-                       lambda: _entry(lib, "intra_group", f.dtype)(
-                           _cl_ptr(f), _lib.dev_ptr(idx32, "intra_idx", torch.int32), ctypes.c_void_p(G.data_ptr()),
-                           b, p, na, kn, c, _lib.stream_of(f))), "intra_group")
+    _run(("intra_group", (b, p, na, kn, c), 0.0, f.device), "intra_group", _entry(lib, "intra_group", f.dtype), _cl_ptr(f),
+         _lib.dev_ptr(idx32, "intra_idx", torch.int32), ctypes.c_void_p(G.data_ptr()), b, p, na, kn, c, _lib.stream_of(f))
     return G
 
 
@@ -904,9 +933,7 @@ class IntraSO3ConvSplitFn(torch.autograd.Function):
         b, cin, p, na = f.shape
         cout = Wc.shape[0]
         kn = intra_idx32.shape[1]
-        if Wc.shape[1] != cin * kn or intra_idx32.shape[0] != na:
-            raise ValueError(f"shape mismatch: feats {tuple(f.shape)}, W {tuple(Wc.shape)}, "
-                             f"intra_idx {tuple(intra_idx32.shape)}")
+        _check_intra_shapes(f, Wc, intra_idx32)
         cols = b * p * na
         G = _intra_group(lib, f, intra_idx32, b, p, na, kn, cin)
         Wp = gemm.cast(Wc.view(cout, cin, kn).permute(0, 2, 1).reshape(cout, kn * cin), f.dtype)     # [o][k*cin + c]
@@ -933,16 +960,7 @@ class IntraSO3ConvSplitFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             inv = inverse_intra_idx(iidx)
             if G.dtype == torch.float32 or inv is None:
-                gf = empty_cl(b, cin, p, na, G.device)
-                g32 = cast_feats(g, torch.float32)
-                ws, wsp, wsn = _intra_ws(lib, na, kn, cin, cout, G.device)
-                _lib.check(_launch("intra_bwd_data", (b, p, na, kn, cin, cout), fl, G.device,
-                                   lambda: lib.epn_intra_so3conv_bwd_data_f32(
-                                       _cl_ptr(g32), _lib.dev_ptr(iidx, "intra_idx", torch.int32),
-                                       _lib.dev_ptr(inv, "inv_idx", torch.int32), _lib.dev_ptr(Wc, "W"),
-                                       b, p, na, kn, cin, cout, _cl_ptr(gf), wsp, wsn, _lib.stream_of(G))),
-                           "intra_so3conv_bwd_data")
-                gf = cast_feats(gf, G.dtype)
+                gf = cast_feats(_intra_fused_bwd_data(lib, cast_feats(g, torch.float32), iidx, inv, Wc, cin), G.dtype)
             else:
                 # dF[col][ci] = sum_{k,o} dOut[pt, inv[a,k], o] W[o, ci*kn + k]: gather through the inverse permutation,
                 # then an NT GEMM against W re-ordered to [ci][k*cout + o]
@@ -1009,25 +1027,17 @@ def _tag_amax(t, amax):
 def _basis_call(lib, src, M, basis, pts, c, in_spec, out_spec, dst, kind):
     if src.dtype != dst.dtype or src.dtype not in FEATURE_DTYPES:
         raise TypeError(f"so3_basis: {src.dtype} -> {dst.dtype}")
+    rec = (kind, ("so3_basis", pts, c), 2.0 * pts * basis.na * basis.na * c, src.device)
+    args = (ctypes.c_void_p(src.data_ptr()), _lib.dev_ptr(M, "M"), _lib.dev_ptr(basis.blocks, "blocks", torch.int32),
+            ctypes.c_longlong(pts), basis.na, c, in_spec, out_spec, ctypes.c_void_p(dst.data_ptr()))
     if out_spec and gemm.f16x2_on(dst):
         # a spectral buffer is the operand of two-piece fp16 GEMMs: its maximum from this kernel's accumulators, not from a
         # pass over the 250 MB it writes
         amax = torch.empty(1, dtype=torch.float32, device=dst.device)
-        _lib.check(_launch(kind, ("so3_basis", pts, c), 2.0 * pts * basis.na * basis.na * c, src.device,
-                           lambda: lib.epn_so3_basis_amax_split_f32(ctypes.c_void_p(src.data_ptr()), _lib.dev_ptr(M, "M"),
-                                                                    _lib.dev_ptr(basis.blocks, "blocks", torch.int32),
-                                                                    ctypes.c_longlong(pts), basis.na, c, in_spec, out_spec,
-                                                                    ctypes.c_void_p(dst.data_ptr()), amax.data_ptr(),
-                                                                    _lib.stream_of(src))), "so3_basis_amax")
+        _run(rec, "so3_basis_amax", lib.epn_so3_basis_amax_split_f32, *args, amax.data_ptr(), _lib.stream_of(src))
         _tag_amax(dst, amax)
         return
-    fn = _entry(lib, "so3_basis", src.dtype)
-    _lib.check(_launch(kind, ("so3_basis", pts, c), 2.0 * pts * basis.na * basis.na * c, src.device,
-                       lambda: fn(ctypes.c_void_p(src.data_ptr()), _lib.dev_ptr(M, "M"),
-                                                     _lib.dev_ptr(basis.blocks, "blocks", torch.int32),
-                                                     ctypes.c_longlong(pts), basis.na, c, in_spec, out_spec,
-                                                     ctypes.c_void_p(dst.data_ptr()), _lib.stream_of(src))),
-               "so3_basis")
+    _run(rec, "so3_basis", _entry(lib, "so3_basis", src.dtype), *args, _lib.stream_of(src))
 
 
 class ToSpectralFn(torch.autograd.Function):
@@ -1068,12 +1078,10 @@ class FromSpectralFn(torch.autograd.Function):
         # + per-point partials of out's per-channel statistics, from the accumulators (epn_so3_basis_stats_*)
         part = torch.empty((b * p, c, 2), dtype=torch.float32, device=y.device)
         src = y.contiguous()
-        fn = _entry(lib, "so3_basis_stats", src.dtype)
-        _lib.check(_launch("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * basis.na * basis.na * c, src.device,
-                           lambda: fn(ctypes.c_void_p(src.data_ptr()), _lib.dev_ptr(basis.U, "M"),
-                                      _lib.dev_ptr(basis.blocks, "blocks", torch.int32), ctypes.c_longlong(b * p), basis.na,
-                                      c, 1, 0, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(part.data_ptr()),
-                                      _lib.stream_of(src))), "so3_basis_stats")
+        _run(("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * basis.na * basis.na * c, src.device), "so3_basis_stats",
+             _entry(lib, "so3_basis_stats", src.dtype), ctypes.c_void_p(src.data_ptr()), _lib.dev_ptr(basis.U, "M"),
+             _lib.dev_ptr(basis.blocks, "blocks", torch.int32), ctypes.c_longlong(b * p), basis.na, c, 1, 0,
+             ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(part.data_ptr()), _lib.stream_of(src))
         ctx.mark_non_differentiable(part)
         return out, part
 
@@ -1234,8 +1242,7 @@ def intra_so3conv_spectral(feats, W, intra_idx32, basis, pre_norm=None, pre_slop
     f = to_cl(feats)
     b, cin, p, na = f.shape
     cout, kn = W.shape[0], intra_idx32.shape[1]
-    if W.shape[1] != cin * kn or intra_idx32.shape[0] != na:
-        raise ValueError(f"shape mismatch: feats {tuple(f.shape)}, W {tuple(W.shape)}, intra_idx {tuple(intra_idx32.shape)}")
+    _check_intra_shapes(f, W, intra_idx32)
     pts = b * p
     if pre_norm is not None:
         # the block's preceding norm + leaky_relu, folded into the transform's loads (training-mode statistics)
@@ -1372,14 +1379,14 @@ class NormActPairFn(torch.autograd.Function):
         dba = torch.empty(c, **f32) if ba is not None else None
         dgb = torch.empty(c, **f32) if gb is not None else None
         dbb = torch.empty(c, **f32) if bb is not None else None
-        ws = torch.empty(max(int(lib.epn_norm_pair_workspace_bytes(b, rows, c)), 16), dtype=torch.uint8, device=dev)
+        ws, wsp, wsn = _ws(lib.epn_norm_pair_workspace_bytes(b, rows, c), dev)
         st = _lib.stream_of(xac)
         _lib.check(lib.epn_norm_act_pair_bwd_reduce(_cl_ptr(xac), _cl_ptr(xbc), _cl_ptr(dy), b, rows, c, ctypes.byref(sa),
                                                     ctypes.byref(sb), slope, _lib.dev_ptr(dsa, "dsums_a"),
                                                     _lib.dev_ptr(dga, "dgamma_a"), _lib.dev_ptr(dba, "dbeta_a"),
                                                     _lib.dev_ptr(dsb, "dsums_b"), _lib.dev_ptr(dgb, "dgamma_b"),
-                                                    _lib.dev_ptr(dbb, "dbeta_b"), ctypes.c_void_p(ws.data_ptr()),
-                                                    ctypes.c_size_t(ws.numel()), bf, st), "norm_act_pair_bwd_reduce")
+                                                    _lib.dev_ptr(dbb, "dbeta_b"), wsp, wsn, bf, st),
+                   "norm_act_pair_bwd_reduce")
         dxa = torch.empty_like(xac) if ctx.needs_input_grad[0] else None
         dxb = torch.empty_like(xbc) if ctx.needs_input_grad[1] else None
         if dxa is not None or dxb is not None:
@@ -1422,9 +1429,8 @@ def _chan_stats(xc, groups, rows, c):
     """sums[g][c] = (sum x, sum x^2) of a channels-last tensor (epn_chan_stats_*: block partials + finishing kernel)."""
     lib = _lib.get_lib()
     sums = torch.empty((groups, c, 2), dtype=torch.float32, device=xc.device)
-    ws = torch.empty(max(int(lib.epn_norm_workspace_bytes(groups, rows, c)), 16), dtype=torch.uint8, device=xc.device)
-    _lib.check(_entry(lib, "chan_stats", xc.dtype)(_cl_ptr(xc), groups, rows, c, _lib.dev_ptr(sums, "sums"),
-                                                   ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
+    ws, wsp, wsn = _ws(lib.epn_norm_workspace_bytes(groups, rows, c), xc.device)
+    _lib.check(_entry(lib, "chan_stats", xc.dtype)(_cl_ptr(xc), groups, rows, c, _lib.dev_ptr(sums, "sums"), wsp, wsn,
                                                    _lib.stream_of(xc)), "chan_stats")
     return sums
 
@@ -1438,9 +1444,9 @@ def sums_from_partials(part, groups, rows, c, block_rows=32):
     lib = _lib.get_lib()
     nb = rows // block_rows
     sums = torch.empty((groups, c, 2), dtype=torch.float32, device=part.device)
-    ws = torch.empty(max(int(lib.epn_stats_finish_workspace_bytes(groups, nb, c)), 16), dtype=torch.uint8, device=part.device)
-    _lib.check(lib.epn_stats_finish(part.data_ptr(), groups, nb, c, sums.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    _lib.stream_of(part)), "stats_finish")
+    ws, wsp, wsn = _ws(lib.epn_stats_finish_workspace_bytes(groups, nb, c), part.device)
+    _lib.check(lib.epn_stats_finish(part.data_ptr(), groups, nb, c, sums.data_ptr(), wsp, wsn, _lib.stream_of(part)),
+               "stats_finish")
     return sums
 
 
@@ -1458,12 +1464,11 @@ def _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, need_dx
     dg = torch.empty(c, dtype=torch.float32, device=xc.device) if g is not None else None
     db = torch.empty(c, dtype=torch.float32, device=xc.device) if bt is not None else None
     gp, bp = _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta")
-    ws = torch.empty(max(int(lib.epn_norm_workspace_bytes(groups, rows, c)), 16), dtype=torch.uint8, device=xc.device)
+    ws, wsp, wsn = _ws(lib.epn_norm_workspace_bytes(groups, rows, c), xc.device)
     _lib.check(_entry(lib, "norm_act_bwd_reduce", xc.dtype)(_cl_ptr(xc), _cl_ptr(dy), groups, rows, c,
                                                _lib.dev_ptr(sums, "sums"), gp, bp, eps, slope,
                                                _lib.dev_ptr(dsums, "dsums"), _lib.dev_ptr(dg, "dgamma"),
-                                               _lib.dev_ptr(db, "dbeta"), ctypes.c_void_p(ws.data_ptr()),
-                                               ctypes.c_size_t(ws.numel()), st), "norm_act_bwd_reduce")
+                                               _lib.dev_ptr(db, "dbeta"), wsp, wsn, st), "norm_act_bwd_reduce")
     dx = None
     if need_dx:
         dx = torch.empty_like(xc)
@@ -1489,23 +1494,16 @@ class NormToSpectralFn(torch.autograd.Function):
         g = gamma.contiguous() if gamma is not None else None
         bt = beta.contiguous() if beta is not None else None
         y = torch.empty(na * b * p * c, dtype=xc.dtype, device=xc.device)
+        rec = ("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, xc.device)
+        args = (_cl_ptr(xc), _lib.dev_ptr(basis.Ut, "M"), _lib.dev_ptr(basis.blocks, "blocks", torch.int32),
+                ctypes.c_longlong(b * p), na, c, 1, ctypes.c_void_p(y.data_ptr()), _lib.dev_ptr(sums, "sums"), groups,
+                ctypes.c_longlong(p), _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), float(eps), float(slope))
         if gemm.f16x2_on(y):                                 # + max|y| for the two-piece GEMMs that read it (see _basis_call)
             amax = torch.empty(1, dtype=torch.float32, device=y.device)
-            _lib.check(_launch("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, xc.device,
-                               lambda: lib.epn_so3_basis_norm_amax_split_f32(
-                                   _cl_ptr(xc), _lib.dev_ptr(basis.Ut, "M"), _lib.dev_ptr(basis.blocks, "blocks", torch.int32),
-                                   ctypes.c_longlong(b * p), na, c, 1, ctypes.c_void_p(y.data_ptr()), _lib.dev_ptr(sums, "sums"),
-                                   groups, ctypes.c_longlong(p), _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), float(eps),
-                                   float(slope), amax.data_ptr(), _lib.stream_of(xc))), "so3_basis_norm_amax")
+            _run(rec, "so3_basis_norm_amax", lib.epn_so3_basis_norm_amax_split_f32, *args, amax.data_ptr(), _lib.stream_of(xc))
             _tag_amax(y, amax)
         else:
-            fn = _entry(lib, "so3_basis_norm", xc.dtype)
-            _lib.check(_launch("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, xc.device,
-                               lambda: fn(_cl_ptr(xc), _lib.dev_ptr(basis.Ut, "M"), _lib.dev_ptr(basis.blocks, "blocks", torch.int32),
-                                          ctypes.c_longlong(b * p), na, c, 1, ctypes.c_void_p(y.data_ptr()),
-                                          _lib.dev_ptr(sums, "sums"), groups, ctypes.c_longlong(p),
-                                          _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), float(eps), float(slope),
-                                          _lib.stream_of(xc))), "so3_basis_norm")
+            _run(rec, "so3_basis_norm", _entry(lib, "so3_basis_norm", xc.dtype), *args, _lib.stream_of(xc))
         ctx.save_for_backward(xc, sums, g, bt)
         ctx.basis = basis
         ctx.cfg = (groups, rows, c, float(eps), float(slope), conv_bias is not None, (b, c, p, na))
@@ -1527,21 +1525,19 @@ class NormToSpectralFn(torch.autograd.Function):
             # (epn_so3_basis_dstats_*): no norm_act_bwd_reduce pass over x and dy
             gyc = cast_feats(gy.contiguous(), xc.dtype)
             pd = torch.empty((b * p, c, 2), dtype=torch.float32, device=gy.device)
-            fn = _entry(lib, "so3_basis_dstats", xc.dtype)
-            _lib.check(_launch("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, gy.device,
-                               lambda: fn(ctypes.c_void_p(gyc.data_ptr()), _lib.dev_ptr(ctx.basis.U, "M"),
-                                          _lib.dev_ptr(ctx.basis.blocks, "blocks", torch.int32), ctypes.c_longlong(b * p), na, c,
-                                          _cl_ptr(gf), _cl_ptr(xc), _lib.dev_ptr(sums, "sums"), groups, ctypes.c_longlong(p),
-                                          _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), float(eps), float(slope),
-                                          pd.data_ptr(), _lib.stream_of(gf))), "so3_basis_dstats")
+            _run(("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, gy.device), "so3_basis_dstats",
+                 _entry(lib, "so3_basis_dstats", xc.dtype), ctypes.c_void_p(gyc.data_ptr()), _lib.dev_ptr(ctx.basis.U, "M"),
+                 _lib.dev_ptr(ctx.basis.blocks, "blocks", torch.int32), ctypes.c_longlong(b * p), na, c, _cl_ptr(gf), _cl_ptr(xc),
+                 _lib.dev_ptr(sums, "sums"), groups, ctypes.c_longlong(p), _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"),
+                 float(eps), float(slope), pd.data_ptr(), _lib.stream_of(gf))
             dsums = torch.empty_like(sums)
             dg = torch.empty(c, dtype=torch.float32, device=gy.device) if g is not None else None
             db = torch.empty(c, dtype=torch.float32, device=gy.device) if bt is not None else None
             bpg = b * p // groups
-            ws = torch.empty(max(int(lib.epn_stats_finish_workspace_bytes(groups, bpg, c)), 16), dtype=torch.uint8, device=gy.device)
+            ws, wsp, wsn = _ws(lib.epn_stats_finish_workspace_bytes(groups, bpg, c), gy.device)
             _lib.check(lib.epn_norm_bwd_finish(pd.data_ptr(), groups, ctypes.c_longlong(bpg), c, _lib.dev_ptr(g, "gamma"),
                                                _lib.dev_ptr(dsums, "dsums"), _lib.dev_ptr(dg, "dgamma"), _lib.dev_ptr(db, "dbeta"),
-                                               ws.data_ptr(), ws.numel(), _lib.stream_of(gf)), "norm_bwd_finish")
+                                               wsp, wsn, _lib.stream_of(gf)), "norm_bwd_finish")
             dx = torch.empty_like(xc)
             if gemm.f16x2_on(dx):      # dx is the inter convolution's output gradient: the narrow operand of two backward GEMMs
                 amax = torch.empty(1, dtype=torch.float32, device=dx.device)
@@ -1628,10 +1624,39 @@ def group_packed():
 
 
 def inter_mode():
-    """EPN_INTER_MODE = fused | split | auto (default).  auto: the split form (grouped features to HBM + library GEMMs)
-    for every layer the MFMA grouping kernel takes (cin % 16 == 0) -- measured faster for training and for inference;
-    the fused kernels are the memory-lean choice (no [cols, cin*ks] tensor) and serve cin = 1 and dense inter_w."""
+    """EPN_INTER_MODE = fused | split | onchip | auto (default); select_inter_fwd holds the rules.  auto: the split form
+    (grouped features to HBM + library GEMMs) for every layer the MFMA grouping kernel takes (cin % 16 == 0) -- measured
+    faster for training and for inference; the fused kernels are the memory-lean choice (no [cols, cin*ks] tensor) and serve
+    cin = 1 and dense inter_w; onchip: the grouping as the A-tile producer of the weight contraction where that kernel
+    takes the layer (inter_onchip_ok)."""
     return os.environ.get("EPN_INTER_MODE", "auto")
+
+
+def select_inter_fwd(cin, dtype, dense, is_cuda, mode, fp32_mode, share_input, requires_grad, share_switch, g_bytes,
+                     device_bytes, onchip_lib_ok):
+    """Which form does InterSO3Conv take?  -> (form, cast): fused (InterSO3ConvFn) | split | split_shared | split_stats
+    (InterSO3ConvSplitFn without / with its share_input) | onchip (InterSO3ConvOnChipFn); cast: the features go to fp32
+    first (shapes only the fp32 fused / generic kernels take).  dense: user-supplied inter_w; mode: EPN_INTER_MODE;
+    share_switch: EPN_SHARE_INPUT_GRAD; g_bytes: size of the fp32 grouped tensor [cols, cin*ks]; device_bytes(), onchip_lib_ok():
+    the device's memory, epn_inter_onchip_ok -- called only where a rule needs them (fp32 auto split candidates; onchip).
+    The split form keeps grouped[cols, cin*ks] (and its gradient) alive: 6 GB per layer at B=32 on the ModelNet schedule.
+    In auto mode an fp32 layer whose grouped tensor would take more than an eighth of the device falls back to the fused
+    kernels, which never materialise it (small-memory parts, very large batches)."""
+    split_ok = cin % 16 == 0 and not dense
+    too_large = split_ok and mode == "auto" and is_cuda and dtype != torch.bfloat16 and g_bytes > device_bytes() // 8
+    if (share_input and split_ok and is_cuda and mode in ("auto", "split") and dtype in FEATURE_DTYPES and share_switch == "1"
+            and not too_large):
+        # no gradient flows back into the features (frozen / detached trunk): handing them out as a differentiable output
+        # would make them require grad through W and cost a discarded dA GEMM (+ scatter) in the skip branch's backward
+        return ("split_shared" if requires_grad else "split_stats"), False
+    if mode == "onchip" and split_ok and _onchip_takes(dtype, dense, is_cuda, fp32_mode, onchip_lib_ok):
+        return "onchip", False
+    if dtype == torch.bfloat16 and split_ok:
+        return "split", False
+    cast = dtype != torch.float32
+    if split_ok and mode in ("split", "auto") and not too_large:
+        return "split", cast
+    return "fused", cast
 
 
 def inter_so3conv(feats, W, geo, out_dtype=None, share_input=False):
@@ -1640,48 +1665,27 @@ def inter_so3conv(feats, W, geo, out_dtype=None, share_input=False):
     feats' is `feats` for the caller's OTHER uses of it (InterSO3ConvSplitFn.forward: its gradient is then folded into the
     convolution's own data gradient; the forms without that fold return `feats` itself) and part the block partials of
     out's per-channel statistics from the GEMM epilogue (or None)."""
-    if share_input:
-        mode = inter_mode()
-        plain = (feats.shape[1] % 16 != 0 or isinstance(geo, DenseInterWeights) or not feats.is_cuda or mode not in ("auto", "split")
-                 or feats.dtype not in FEATURE_DTYPES or ab("EPN_SHARE_INPUT_GRAD") != "1")
-        if not plain and feats.dtype == torch.float32:
-            g_bytes = (geo.ball_idx.shape[0] * geo.ball_idx.shape[1] * geo.anchors.shape[0] * feats.shape[1] *
-                       geo.kernels.shape[0] * 4)
-            plain = mode == "auto" and g_bytes > _device_bytes(feats.device) // 8
-        if plain:
-            return inter_so3conv(feats, W, geo, out_dtype), feats, None
-        if not feats.requires_grad:
-            # nothing flows back into `feats` (frozen / detached trunk): handing it out as a differentiable output would make
-            # it require grad through W and cost a discarded dA GEMM (+ scatter) in the skip branch's backward
-            out, part = InterSO3ConvSplitFn.apply(feats, W, geo, "stats")
-            shared = feats
-        else:
-            out, shared, part = InterSO3ConvSplitFn.apply(feats, W, geo, True)
-            if out.grad_fn is not None:
-                out.grad_fn.shared_ref = weakref.ref(shared)    # backward(): is anybody watching this tensor's gradient?
-        if (out_dtype or feats.dtype) != out.dtype:
-            return cast_feats(out, out_dtype), shared, None      # statistics must be those of the values handed on
-        return out, shared, (part if part.numel() else None)
-    mode = inter_mode()
+    cin, dense = feats.shape[1], isinstance(geo, DenseInterWeights)
+    g_bytes = 0 if dense else geo.ball_idx.shape[0] * geo.ball_idx.shape[1] * geo.anchors.shape[0] * cin * geo.kernels.shape[0] * 4
+    form, cast = select_inter_fwd(cin, feats.dtype, dense, feats.is_cuda, inter_mode(), gemm.FP32_MODE, bool(share_input),
+                                  feats.requires_grad, ab("EPN_SHARE_INPUT_GRAD") if share_input else None, g_bytes,
+                                  lambda: _device_bytes(feats.device), lambda: _onchip_lib_ok(feats, W, geo))
     out_dtype = out_dtype or feats.dtype
-    split_ok = feats.shape[1] % 16 == 0 and not isinstance(geo, DenseInterWeights)
-    if mode == "onchip" and split_ok and inter_onchip_ok(feats, W, geo):
-        return cast_feats(InterSO3ConvOnChipFn.apply(feats, W, geo), out_dtype)
-    if feats.dtype == torch.bfloat16 and split_ok:
-        return cast_feats(InterSO3ConvSplitFn.apply(feats, W, geo), out_dtype)
-    if feats.dtype != torch.float32:         # shapes only the fp32 fused / generic kernels take
-        feats = cast_feats(feats, torch.float32)
-    if split_ok and mode == "auto" and feats.is_cuda:
-        # the split form keeps grouped[cols, cin*ks] (and its gradient) alive: 6 GB per layer at B=32 on the ModelNet
-        # schedule.  A layer whose grouped tensor would take more than an eighth of the device falls back to the fused
-        # kernels, which never materialise it (small-memory parts, very large batches).
-        d_b, d_p2 = geo.ball_idx.shape[0], geo.ball_idx.shape[1]
-        g_bytes = d_b * d_p2 * geo.anchors.shape[0] * feats.shape[1] * geo.kernels.shape[0] * 4
-        if g_bytes > _device_bytes(feats.device) // 8:
-            split_ok = False
-    if split_ok and mode in ("split", "auto"):
-        return cast_feats(InterSO3ConvSplitFn.apply(feats, W, geo), out_dtype)
-    return cast_feats(InterSO3ConvFn.apply(feats, W, geo), out_dtype)
+    shared, part = feats, None
+    if form == "split_stats":
+        out, part = InterSO3ConvSplitFn.apply(feats, W, geo, "stats")
+    elif form == "split_shared":
+        out, shared, part = InterSO3ConvSplitFn.apply(feats, W, geo, True)
+        if out.grad_fn is not None:
+            out.grad_fn.shared_ref = weakref.ref(shared)    # backward(): is anybody watching this tensor's gradient?
+    else:
+        fn = {"fused": InterSO3ConvFn, "split": InterSO3ConvSplitFn, "onchip": InterSO3ConvOnChipFn}[form]
+        out = fn.apply(cast_feats(feats, torch.float32) if cast else feats, W, geo)
+    if out.dtype != out_dtype:
+        out, part = cast_feats(out, out_dtype), None             # statistics must be those of the values handed on
+    elif part is not None and not part.numel():
+        part = None
+    return (out, shared, part) if share_input else out
 
 
 _DEVICE_BYTES = {}
@@ -1695,21 +1699,29 @@ def _device_bytes(device):
 
 
 def intra_mode():
-    """EPN_INTRA_MODE = fused | split | spectral | auto (default).  auto: the block-diagonal ("spectral") form when both
-    widths are multiples of 32 and the index table is a regular group action, else the split form (gather kernel +
-    library GEMMs) for multiples of 16, else the fused / generic kernels."""
+    """EPN_INTRA_MODE = fused | split | spectral | auto (default); select_intra holds the rules.  auto: the block-diagonal
+    ("spectral") form when both widths are multiples of 32 and the index table is a regular group action, else the split
+    form (gather kernel + library GEMMs) for multiples of 16, else the fused / generic kernels."""
     return os.environ.get("EPN_INTRA_MODE", "auto")
 
 
-def intra_so3conv_fused(feats, W, intra_idx32):
-    return IntraSO3ConvFn.apply(feats, W, intra_idx32)
+def select_intra(cin, cout, kn, is_cuda, mode, basis_ok, bf16=False):
+    """Which form does IntraSO3Conv take?  -> spectral (intra_so3conv_spectral) | split (IntraSO3ConvSplitFn) | fused
+    (IntraSO3ConvFn; bf16 features of odd widths: between two casts).  kn: intra_idx.shape[1]; mode: EPN_INTRA_MODE;
+    basis_ok(): spectral_basis has a basis for the table -- called only where the other conditions of the form hold."""
+    auto = mode in ("auto", "spectral")
+    if auto and is_cuda and cin % 32 == 0 and cout % 32 == 0 and kn > 1 and basis_ok():
+        return "spectral"
+    if (bf16 and cin % 8 == 0 and cout % 8 == 0) or mode == "split" or (auto and cin % 16 == 0 and cout % 16 == 0):
+        return "split"
+    return "fused"
 
 
 def intra_takes_spectral(cin, cout, intra_idx32, is_cuda=True):
     """Will intra_so3conv run the block-diagonal form for these widths / this table?  (Then a preceding norm + leaky_relu
     can be folded into its basis change: intra_so3conv(..., pre_norm=).)"""
-    return (intra_mode() in ("auto", "spectral") and is_cuda and cin % 32 == 0 and cout % 32 == 0
-            and intra_idx32.shape[1] > 1 and spectral_basis(intra_idx32) is not None)
+    return select_intra(cin, cout, intra_idx32.shape[1], is_cuda, intra_mode(),
+                        lambda: spectral_basis(intra_idx32) is not None) == "spectral"
 
 
 def intra_so3conv(feats, W, intra_idx32, pre_norm=None, pre_part=None, out_stats=False):
@@ -1717,30 +1729,21 @@ def intra_so3conv(feats, W, intra_idx32, pre_norm=None, pre_part=None, out_stats
     (training mode); only with intra_takes_spectral(...) -- other forms get the normalised tensor from ops.norm_act.
     pre_part: block partials of feats' per-channel statistics from its producer's epilogue (spectral form only).
     out_stats: return (out, part) -- part = per-point partials of out's statistics (spectral form) or None."""
-    if out_stats:
-        mode = intra_mode()
-        cin, cout = feats.shape[1], W.shape[0]
-        if mode in ("auto", "spectral") and feats.is_cuda and cin % 32 == 0 and cout % 32 == 0 and intra_idx32.shape[1] > 1:
-            basis = spectral_basis(intra_idx32)
-            if basis is not None:
-                return intra_so3conv_spectral(feats, W, intra_idx32, basis, pre_norm=pre_norm, pre_part=pre_part,
-                                              out_stats=True)
-        return intra_so3conv(feats, W, intra_idx32, pre_norm, pre_part), None
-    mode = intra_mode()
-    cin, cout = feats.shape[1], W.shape[0]
     bf = feats.dtype == torch.bfloat16
-    if mode in ("auto", "spectral") and feats.is_cuda and cin % 32 == 0 and cout % 32 == 0 and intra_idx32.shape[1] > 1:
-        basis = spectral_basis(intra_idx32)
-        if basis is not None:
-            return intra_so3conv_spectral(feats, W, intra_idx32, basis, pre_norm=pre_norm, pre_part=pre_part)
+    form = select_intra(feats.shape[1], W.shape[0], intra_idx32.shape[1], feats.is_cuda, intra_mode(),
+                        lambda: spectral_basis(intra_idx32) is not None, bf)
+    if form == "spectral":
+        return intra_so3conv_spectral(feats, W, intra_idx32, spectral_basis(intra_idx32), pre_norm=pre_norm,
+                                      pre_part=pre_part, out_stats=out_stats)
     if pre_norm is not None:
         feats = norm_act(feats, pre_norm)
-    if (bf and cin % 8 == 0 and cout % 8 == 0) or mode == "split" or \
-            (mode in ("auto", "spectral") and cin % 16 == 0 and cout % 16 == 0):
-        return IntraSO3ConvSplitFn.apply(feats, W, intra_idx32)
-    if bf:                                   # odd widths: fp32 kernels between two casts
-        return cast_feats(IntraSO3ConvFn.apply(cast_feats(feats, torch.float32), W, intra_idx32), torch.bfloat16)
-    return IntraSO3ConvFn.apply(feats, W, intra_idx32)
+    if form == "split":
+        out = IntraSO3ConvSplitFn.apply(feats, W, intra_idx32)
+    elif bf:                                   # odd widths: fp32 kernels between two casts
+        out = cast_feats(IntraSO3ConvFn.apply(cast_feats(feats, torch.float32), W, intra_idx32), torch.bfloat16)
+    else:
+        out = IntraSO3ConvFn.apply(feats, W, intra_idx32)
+    return (out, None) if out_stats else out
 
 
 class PointnetSO3ConvFn(torch.autograd.Function):
@@ -1767,11 +1770,10 @@ class PointnetSO3ConvFn(torch.autograd.Function):
         arg = torch.empty((b, a, co), dtype=torch.int32, device=fc.device)
         ctr = torch.empty((b, 3), dtype=torch.float32, device=fc.device)
         bs = bias.contiguous() if bias is not None else None
-        _launch("pointnet_fwd", ("pointnet", b, p, a, c, co), 2.0 * b * p * a * co * (c + 3), fc.device,
-                lambda: _lib.check(lib.epn_pointnet_so3conv_fwd_f32(
-                    _cl_ptr(fc), _lib.dev_ptr(xyz, "xyz"), _lib.dev_ptr(anc, "anchors"), _lib.dev_ptr(w, "weight"),
-                    _lib.dev_ptr(bs, "bias"), _lib.dev_ptr(out, "out"), _lib.dev_ptr(arg, "argmax", torch.int32),
-                    _lib.dev_ptr(ctr, "centre"), b, p, a, c, co, _lib.stream_of(fc)), "pointnet_so3conv_fwd"))
+        _run(("pointnet_fwd", ("pointnet", b, p, a, c, co), 2.0 * b * p * a * co * (c + 3), fc.device), "pointnet_so3conv_fwd",
+             lib.epn_pointnet_so3conv_fwd_f32, _cl_ptr(fc), _lib.dev_ptr(xyz, "xyz"), _lib.dev_ptr(anc, "anchors"),
+             _lib.dev_ptr(w, "weight"), _lib.dev_ptr(bs, "bias"), _lib.dev_ptr(out, "out"),
+             _lib.dev_ptr(arg, "argmax", torch.int32), _lib.dev_ptr(ctr, "centre"), b, p, a, c, co, _lib.stream_of(fc))
         ctx.save_for_backward(fc, xyz, anc, w, arg, ctr)
         ctx.cfg = (b, p, a, c, co, tuple(weight.shape), bias is not None)
         return out.permute(0, 2, 1)
@@ -1786,19 +1788,16 @@ class PointnetSO3ConvFn(torch.autograd.Function):
         dF = dW = db = None
         if ctx.needs_input_grad[0]:
             dF = torch.empty_like(fc)
-            _launch("pointnet_bwd_data", ("pointnet", b, p, a, c, co), 2.0 * b * a * co * c, fc.device,
-                    lambda: _lib.check(lib.epn_pointnet_so3conv_bwd_data_f32(
-                        _lib.dev_ptr(g, "grad_out"), _lib.dev_ptr(arg, "argmax", torch.int32), _lib.dev_ptr(w, "weight"),
-                        _cl_ptr(dF), b, p, a, c, co, st), "pointnet_so3conv_bwd_data"))
+            _run(("pointnet_bwd_data", ("pointnet", b, p, a, c, co), 2.0 * b * a * co * c, fc.device), "pointnet_so3conv_bwd_data",
+                 lib.epn_pointnet_so3conv_bwd_data_f32, _lib.dev_ptr(g, "grad_out"), _lib.dev_ptr(arg, "argmax", torch.int32),
+                 _lib.dev_ptr(w, "weight"), _cl_ptr(dF), b, p, a, c, co, st)
         if ctx.needs_input_grad[3] or (has_bias and ctx.needs_input_grad[4]):
             dW = torch.empty((co, c + 3), dtype=torch.float32, device=fc.device)
             db = torch.empty(co, dtype=torch.float32, device=fc.device) if has_bias else None
-            _launch("pointnet_bwd_weight", ("pointnet", b, p, a, c, co), 2.0 * b * a * co * (c + 3), fc.device,
-                    lambda: _lib.check(lib.epn_pointnet_so3conv_bwd_weight_f32(
-                        _lib.dev_ptr(g, "grad_out"), _lib.dev_ptr(arg, "argmax", torch.int32), _cl_ptr(fc),
-                        _lib.dev_ptr(xyz, "xyz"), _lib.dev_ptr(anc, "anchors"), _lib.dev_ptr(ctr, "centre"),
-                        _lib.dev_ptr(dW, "grad_W"), _lib.dev_ptr(db, "grad_bias"), b, p, a, c, co, st),
-                        "pointnet_so3conv_bwd_weight"))
+            _run(("pointnet_bwd_weight", ("pointnet", b, p, a, c, co), 2.0 * b * a * co * (c + 3), fc.device),
+                 "pointnet_so3conv_bwd_weight", lib.epn_pointnet_so3conv_bwd_weight_f32, _lib.dev_ptr(g, "grad_out"),
+                 _lib.dev_ptr(arg, "argmax", torch.int32), _cl_ptr(fc), _lib.dev_ptr(xyz, "xyz"), _lib.dev_ptr(anc, "anchors"),
+                 _lib.dev_ptr(ctr, "centre"), _lib.dev_ptr(dW, "grad_W"), _lib.dev_ptr(db, "grad_bias"), b, p, a, c, co, st)
             dW = dW.view(wshape)
         return dF, None, None, dW, db
 
