@@ -1,4 +1,5 @@
-// Internal interface of gemm.hip (the BasicSO3Conv weight contractions as MFMA GEMMs).
+// Internal interface of the GEMM translation units (the BasicSO3Conv weight contractions as MFMA GEMMs): gemm.hip (NT, casts),
+// gemm_tn.hip (TN weight gradients), gemm_x3.hip / gemm_pp.hip (split forms), and the device parts they share.
 #pragma once
 #include "epn_common.h"
 
@@ -44,6 +45,48 @@ struct GemmTnBatch {       // up to GEMM_MAX_PROB problems in ONE launch (the ir
 };
 
 #ifdef __HIPCC__
+// ---- parts every GEMM kernel is built from
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(1))) const void glb_void;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+template <typename T> struct ElemOf;
+template <> struct ElemOf<float> { static constexpr int PER16 = 4; };
+template <> struct ElemOf<__bf16> { static constexpr int PER16 = 8; };
+
+// direct-to-LDS load: 16 bytes per lane, one 1 KiB wave instruction (global_load_lds_dwordx4)
+__device__ __forceinline__ void glds16(const void *g, char *lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((glb_void *)g, (lds_void *)lds_wave_base, 16, 0, 0);
+}
+__device__ __forceinline__ void glds16_nt(const void *g, char *lds_wave_base) {      // non-temporal: a stream read once
+    __builtin_amdgcn_global_load_lds((glb_void *)g, (lds_void *)lds_wave_base, 16, 0, 2);
+}
+
+// lossless split of fp32 into three bf16 pieces x = h + m + l (gemm_x3.hip): pairs packed as v_cvt_pk_bf16_f32 leaves them
+__device__ __forceinline__ unsigned pack_rne(float a, float b) {   // v_cvt_pk_bf16_f32
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+__device__ __forceinline__ float lo_f(unsigned p) { return __builtin_bit_cast(float, p << 16); }
+__device__ __forceinline__ float hi_f(unsigned p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
+// eight fp32 values -> three bf16x8 fragments (4.5 VALU instructions per value)
+__device__ __forceinline__ void split3(const float (&x)[8], bf16x8 &h, bf16x8 &m, bf16x8 &l) {
+    u32x4 H, M, L;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const unsigned hp = pack_rne(x[2 * p], x[2 * p + 1]);
+        const float r0 = x[2 * p] - lo_f(hp), r1 = x[2 * p + 1] - hi_f(hp);
+        const unsigned mp = pack_rne(r0, r1);
+        H[p] = hp; M[p] = mp; L[p] = pack_rne(r0 - lo_f(mp), r1 - hi_f(mp));
+    }
+    h = __builtin_bit_cast(bf16x8, H); m = __builtin_bit_cast(bf16x8, M); l = __builtin_bit_cast(bf16x8, L);
+}
+
 // ---- two-piece fp16 split ("f16x2", round 5): x 2^s = h + l with h = rne_f16(x 2^s), l = rne_f16(x 2^s - h) keeps 22-23
 // significant bits of every element within 2^-17 of the tensor's largest magnitude (absolute error <= max|x| 2^-39 below
 // that); a product is hh + hl + lh on v_mfma_f32_32x32x16_f16 -- THREE matrix instructions per 32 x 32 x 16 block where the
@@ -90,8 +133,21 @@ __device__ __forceinline__ void f2_split8(const float (&x)[8], float s, gemm_f16
 // an accumulator was inf or NaN -- one VALU instruction per accumulator and TILE, nothing per K step) and a wave with a
 // non-finite accumulator bumps a sticky device counter (one atomic per wave, only then).  With finite operands a non-zero
 // count can only be a violated scale contract; epn_f16x2_overflow_count() reads (and optionally clears) the sum over the
-// library's two GEMM translation units.  Each TU owns its counter (no relocatable device code in this build).
+// library's three translation units that use it (gemm_tn.hip, gemm_x3.hip, inter_bwd_f2.hip).  Each TU owns its counter (no relocatable device code in this build).
 #define EPN_F2_SENTINEL_DECL __device__ unsigned g_f2_nonfinite = 0u;
+// the TU's `take` function (declared below): read its counter synchronously on the current device, optionally clear it
+#define EPN_F2_SENTINEL_TAKE(name_)                                                                                         \
+    long long name_(bool reset) {                                                                                           \
+        unsigned v = 0;                                                                                                     \
+        hipError_t e = hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_f2_nonfinite), sizeof(v), 0, hipMemcpyDeviceToHost);            \
+        if (e != hipSuccess) return -(long long)e;                                                                          \
+        if (reset && v) {                                                                                                   \
+            const unsigned zero = 0;                                                                                        \
+            e = hipMemcpyToSymbol(HIP_SYMBOL(g_f2_nonfinite), &zero, sizeof(zero), 0, hipMemcpyHostToDevice);               \
+            if (e != hipSuccess) return -(long long)e;                                                                      \
+        }                                                                                                                   \
+        return (long long)v;                                                                                                \
+    }
 #define EPN_F2_CHECK(chk_)                                                                       \
     do {                                                                                         \
         const float c__ = (chk_);                                                                \
@@ -99,11 +155,63 @@ __device__ __forceinline__ void f2_split8(const float (&x)[8], float s, gemm_f16
             atomicAdd(&g_f2_nonfinite, 1u);                                                      \
     } while (0)
 
+// ---- MFMA term groups of the split forms: one term = every (i, j) tile of the wave; the groups add the small terms first
+typedef float gemm_f32x16 __attribute__((ext_vector_type(16)));
+template <int TM, int TN>
+__device__ __forceinline__ void mfma_term(gemm_f32x16 (&acc)[TM][TN], const bf16x8 (&a)[TM], const bf16x8 (&b)[TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+}
+template <int TM, int TN>
+__device__ __forceinline__ void mfma_term(gemm_f32x16 (&acc)[TM][TN], const gemm_f16x8 (&a)[TM], const gemm_f16x8 (&b)[TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
+}
+// three-piece form: the six terms of weight >= 2^-16 (gemm_x3.hip)
+template <int TM, int TN>
+__device__ __forceinline__ void x3_terms(gemm_f32x16 (&acc)[TM][TN], const bf16x8 (&ah)[TM], const bf16x8 (&am)[TM],
+                                         const bf16x8 (&al)[TM], const bf16x8 (&bh)[TN], const bf16x8 (&bm)[TN],
+                                         const bf16x8 (&bl)[TN]) {
+    mfma_term(acc, ah, bl);
+    mfma_term(acc, al, bh);
+    mfma_term(acc, am, bm);
+    mfma_term(acc, ah, bm);
+    mfma_term(acc, am, bh);
+    mfma_term(acc, ah, bh);
+}
+// two-piece form: hl + lh + hh
+template <int TM, int TN>
+__device__ __forceinline__ void f2_terms(gemm_f32x16 (&acc)[TM][TN], const gemm_f16x8 (&ah)[TM], const gemm_f16x8 (&al)[TM],
+                                         const gemm_f16x8 (&bh)[TN], const gemm_f16x8 (&bl)[TN]) {
+    mfma_term(acc, ah, bl);
+    mfma_term(acc, al, bh);
+    mfma_term(acc, ah, bh);
+}
+// two-piece epilogue with tensor-wide scales: undoes them and returns the fold for EPN_F2_CHECK (NaN iff an accumulator of
+// this lane is inf / NaN)
+template <int TM, int TN>
+__device__ __forceinline__ float f2_unscale(gemm_f32x16 (&acc)[TM][TN], float ux, float uy) {
+    float chk = 0.0f;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                chk = fmaf(acc[i][j][r], 0.0f, chk);
+                acc[i][j][r] = acc[i][j][r] * ux * uy;
+            }
+    return chk;
+}
+
 // Column statistics of an NT tile, taken from the accumulators in the epilogue (the per-channel sums a following
 // BatchNorm / InstanceNorm needs: SURVEY 8f.1 -- no separate pass over C).  acc[i][j]: 32 x 32 MFMA tile i (rows) x j
 // (columns) of the wave, D[row = (r&3) + 8 (r>>2) + 4 lj][col = li]; part[(row / 32)][n][2].  The sums are those of the
 // values as STORED (rounded to bf16 first when C is bf16): what a statistics pass over C would read.
-typedef float gemm_f32x16 __attribute__((ext_vector_type(16)));
 template <int TM, int TN, typename TO>
 __device__ __forceinline__ void nt_col_stats(const gemm_f32x16 (&acc)[TM][TN], float *__restrict__ part, long long M, int N,
                                              long long row0, int col0, int li, int lj) {
@@ -162,8 +270,8 @@ __device__ __forceinline__ void nt_c_amax(const gemm_f32x16 (&acc)[TM][TN], unsi
 #endif
 
 // f16x2 sentinel: sticky per-device count of waves that ended a two-piece GEMM tile with a non-finite accumulator, per TU
-// (gemm.hip, gemm_x3.hip); take = read (synchronously, on the current device) and optionally clear.  < 0: a hipError_t, negated
-long long f2_nonfinite_take_gemm(bool reset);
+// (gemm_tn.hip, gemm_x3.hip); take = read (synchronously, on the current device) and optionally clear.  < 0: a hipError_t, negated
+long long f2_nonfinite_take_gemm(bool reset);   // gemm_tn.hip
 long long f2_nonfinite_take_x3(bool reset);
 long long f2_nonfinite_take_bwd(bool reset);    // inter_bwd_f2.hip
 

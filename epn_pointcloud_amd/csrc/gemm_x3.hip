@@ -23,38 +23,10 @@ namespace epn {
 namespace {
 EPN_F2_SENTINEL_DECL
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds16(const void *g, char *lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((glb_void *)g, (lds_void *)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ void glds16_nt(const void *g, char *lds_wave_base) {      // non-temporal: a stream read once
-    __builtin_amdgcn_global_load_lds((glb_void *)g, (lds_void *)lds_wave_base, 16, 0, 2);
-}
-__device__ __forceinline__ unsigned pack_rne(float a, float b) {   // v_cvt_pk_bf16_f32
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-// eight fp32 values -> three bf16x8 fragments (4.5 VALU instructions per value)
+// two b128 fragment reads -> three bf16x8 fragments (gemm.h split3)
 __device__ __forceinline__ void split3(const f32x4 u, const f32x4 v, bf16x8 &h, bf16x8 &m, bf16x8 &l) {
     const float x[8] = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-    u32x4 H, M, L;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const unsigned hp = pack_rne(x[2 * p], x[2 * p + 1]);
-        const float r0 = x[2 * p] - lo_f(hp), r1 = x[2 * p + 1] - hi_f(hp);
-        const unsigned mp = pack_rne(r0, r1);
-        H[p] = hp; M[p] = mp; L[p] = pack_rne(r0 - lo_f(mp), r1 - hi_f(mp));
-    }
-    h = __builtin_bit_cast(bf16x8, H); m = __builtin_bit_cast(bf16x8, M); l = __builtin_bit_cast(bf16x8, L);
+    epn::split3(x, h, m, l);
 }
 
 // weights -> planes[3][N][K] (bf16), two values per thread
@@ -467,17 +439,7 @@ inline size_t planes_bytes(const GemmNtProb &p) { return ((size_t)6 * p.N * p.K 
 
 }  // namespace
 
-long long f2_nonfinite_take_x3(bool reset) {
-    unsigned v = 0;
-    hipError_t e = hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_f2_nonfinite), sizeof(v), 0, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return -(long long)e;
-    if (reset && v) {
-        const unsigned zero = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_f2_nonfinite), &zero, sizeof(zero), 0, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return -(long long)e;
-    }
-    return (long long)v;
-}
+EPN_F2_SENTINEL_TAKE(f2_nonfinite_take_x3)
 
 bool gemm_nt_x3_ok(const GemmNtBatch &B) {
     for (int i = 0; i < B.nprob; ++i) {

@@ -32,8 +32,6 @@ namespace epn {
 namespace {
 EPN_F2_SENTINEL_DECL
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
 __device__ __forceinline__ void bf_glds16(const void *g, char *lds_wave_base) {
     __builtin_amdgcn_global_load_lds((glb_void *)g, (lds_void *)lds_wave_base, 16, 0, 0);
 }
@@ -504,17 +502,7 @@ size_t planes_bytes(const epn_inter_desc *d) { return ((size_t)4 * d->cin * d->k
 
 }  // namespace
 
-long long f2_nonfinite_take_bwd(bool reset) {
-    unsigned v = 0;
-    hipError_t e = hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_f2_nonfinite), sizeof(v), 0, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return -(long long)e;
-    if (reset && v) {
-        const unsigned zero = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_f2_nonfinite), &zero, sizeof(zero), 0, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return -(long long)e;
-    }
-    return (long long)v;
-}
+EPN_F2_SENTINEL_TAKE(f2_nonfinite_take_bwd)
 
 bool inter_bwd_f2_ok(const epn_inter_desc *d) {
     if (!inter_group_mfma_ok(d)) return false;

@@ -1,5 +1,5 @@
 """BasicSO3Conv's weight contraction (vgtk/vgtk/so3conv/modules.py:48-55) and its autograd transposes on the library's
-own MFMA GEMM kernels (csrc/gemm.hip) -- no torch.mm / BLAS on the path.
+own MFMA GEMM kernels (csrc/gemm.hip, csrc/gemm_tn.hip) -- no torch.mm / BLAS on the path.
 
     gemm_nt(A [M,K], Bt [N,K])  -> A @ Bt.T       activations x weights (fp32, or bf16 with fp32 accumulation)
     gemm_tn(X [R,N1], Y [R,N2]) -> X.T @ Y (fp32) weight gradients: deterministic split over R

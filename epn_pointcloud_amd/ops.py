@@ -394,7 +394,7 @@ class InterSO3ConvSplitFn(torch.autograd.Function):
     """The same convolution as InterSO3ConvFn in the reference's own two steps -- inter_so3conv_grouping, then
     BasicSO3Conv's matmul (vgtk/vgtk/so3conv/modules.py:38-52,157-174) -- with the grouping as ONE HIP kernel that
     writes only the grouped features G[col][cin*ks] (no inter_w, no gathered neighbours) and the three weight
-    contractions (out = G W^T, dW = dOut^T G, dG = dOut W) on this library's own MFMA GEMM kernels (csrc/gemm.hip,
+    contractions (out = G W^T, dW = dOut^T G, dG = dOut W) on this library's own MFMA GEMM kernels (csrc/gemm.hip, csrc/gemm_tn.hip,
     csrc/gemm_x3.hip: fp32 operands in the lossless 3 x bf16 split form by default, 160-200 fp32-equivalent TFLOP/s on the
     schedule's shapes; no BLAS library is involved).  G (cin*ks*4 bytes per column) is kept for the backward pass: the
     training-time choice on a 288 GB part; InterSO3ConvFn / InterSO3ConvOnChipFn are the forms that never write it."""
