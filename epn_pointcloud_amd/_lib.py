@@ -51,6 +51,9 @@ EXPORTS = [
     "epn_inter_split_ok", "epn_inter_split_saved_bytes", "epn_inter_split_workspace_bytes",
     "epn_inter_so3conv_fwd_split_f32", "epn_inter_so3conv_fwd_split_bf16", "epn_inter_so3conv_bwd_split_f32",
     "epn_inter_so3conv_bwd_split_bf16",
+    "epn_norm_act_dropout_fwd_f32", "epn_norm_act_dropout_bwd_reduce_f32", "epn_norm_act_dropout_bwd_apply_f32",
+    "epn_norm_act_dropout_fwd_bf16", "epn_norm_act_dropout_bwd_reduce_bf16", "epn_norm_act_dropout_bwd_apply_bf16",
+    "epn_dropout_mask_u8", "epn_dropout_state_next",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -279,6 +282,16 @@ def get_lib():
     lib.epn_norm_act_fwd_bf16.argtypes = lib.epn_norm_act_fwd_f32.argtypes
     lib.epn_norm_act_bwd_reduce_bf16.argtypes = lib.epn_norm_act_bwd_reduce_f32.argtypes
     lib.epn_norm_act_bwd_apply_bf16.argtypes = lib.epn_norm_act_bwd_apply_f32.argtypes
+    _cd = ctypes.c_double                    # dropout forms: (rate, state) after slope
+    for _t in ("f32", "bf16"):
+        getattr(lib, "epn_norm_act_dropout_fwd_" + _t).argtypes = [_vp, _ci, _ll, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _cd, _vp, _vp, _vp]
+        getattr(lib, "epn_norm_act_dropout_bwd_reduce_" + _t).argtypes = [_vp, _vp, _ci, _ll, _ci, _vp, _vp, _vp, _cf, _cf, _cd, _vp,
+                                                                          _vp, _vp, _vp, _vp, _sz, _vp]
+        getattr(lib, "epn_norm_act_dropout_bwd_apply_" + _t).argtypes = [_vp, _vp, _ci, _ll, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _cd,
+                                                                         _vp, _vp, _vp]
+    lib.epn_dropout_mask_u8.argtypes = [_vp, _ll, _cd, _vp, _vp]
+    lib.epn_dropout_state_next.argtypes = [_vp, _vp, _vp]
+    lib.epn_dropout_mask_u8.restype = lib.epn_dropout_state_next.restype = _ci
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

@@ -215,8 +215,55 @@ __global__ __launch_bounds__(256) void bwd_finish_kernel(const float *__restrict
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(GT) void norm_act_fwd_kernel(NormArgs A) {
+// ---- dropout inside the norm passes (nn.Dropout after every block norm, SPConvNets/utils/base_so3conv.py:58-59 / 124-125).
+// The mask is a pure function of (seed, call, flat channels-last offset e, rate) -- include/epn_so3conv.h states it -- so the
+// backward passes regenerate it instead of reading a stored one: element e is dropped iff word e & 3 of
+// Philox4x32-10(counter {e >> 2, call}, key seed) < floor(rate * 2^32).  A thread's 4 channels sit at an offset that is a
+// multiple of 4: one generator call per 16-byte access.  (seed, call) are read through a pointer, never launch arguments: a
+// captured graph draws a fresh mask on every replay.
+struct DropArgs {
+    const unsigned long long *state;   // device (seed, call)
+    unsigned thresh;                   // floor(rate * 2^32)
+    float scale;                       // 1 / (1 - rate)
+};
+
+struct u32x4 { unsigned w[4]; };
+__device__ __forceinline__ u32x4 philox4x32_10(unsigned long long ctr_lo, unsigned long long ctr_hi, unsigned long long key) {
+    unsigned c0 = (unsigned)ctr_lo, c1 = (unsigned)(ctr_lo >> 32), c2 = (unsigned)ctr_hi, c3 = (unsigned)(ctr_hi >> 32);
+    unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1;
+        c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return u32x4{{c0, c1, c2, c3}};
+}
+
+// (seed, call) as a kernel holds them: read once through DropArgs::state (DROP), nothing otherwise
+template <bool DROP>
+struct DropState {
+    unsigned long long seed = 0, call = 0;
+    __device__ __forceinline__ explicit DropState(const DropArgs &D) {
+        if constexpr (DROP) { seed = D.state[0]; call = D.state[1]; }
+    }
+};
+
+// v * m / (1 - rate) for the 4 elements at flat offset off (a multiple of 4): one generator call; v itself without DROP
+template <bool DROP>
+__device__ __forceinline__ f32x4 drop4(const f32x4 v, const DropArgs &D, const DropState<DROP> &S, size_t off) {
+    if constexpr (!DROP) return v;
+    const u32x4 w = philox4x32_10((unsigned long long)off >> 2, S.call, S.seed);
+    f32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = w.w[i] < D.thresh ? 0.0f : v[i] * D.scale;
+    return o;
+}
+
+template <typename T, bool DROP>
+__device__ __forceinline__ void norm_act_fwd_body(const NormArgs A, const DropArgs D) {
     const int lanes = A.c >> 2, cl = threadIdx.x % lanes, rl = threadIdx.x / lanes, rstep = GT / lanes;
     const int g = blockIdx.y, c4 = 4 * cl;
     f32x4 mean, rstd, ga, be;
@@ -227,6 +274,7 @@ __global__ __launch_bounds__(GT) void norm_act_fwd_kernel(NormArgs A) {
     long long r1 = r0 + A.rows_per_block;
     r1 = r1 < A.rows ? r1 : A.rows;
     const size_t base = ((size_t)g * A.rows) * A.c + c4;
+    const DropState<DROP> S(D);
     for (long long r = r0 + rl; r < r1; r += rstep) {
         const size_t off = base + (size_t)r * A.c;
         const f32x4 v = ld4(static_cast<const T *>(A.x) + off);
@@ -236,6 +284,7 @@ __global__ __launch_bounds__(GT) void norm_act_fwd_kernel(NormArgs A) {
             const float n = (v[i] - mean[i]) * rstd[i] * ga[i] + be[i];
             o[i] = n > 0.0f ? n : n * A.slope;
         }
+        o = drop4<DROP>(o, D, S, off);        // the residual below is added after the mask and is never masked
         if (A.res) {
             const f32x4 rr = ld4(static_cast<const T *>(A.res) + off);
 #pragma unroll
@@ -246,9 +295,9 @@ __global__ __launch_bounds__(GT) void norm_act_fwd_kernel(NormArgs A) {
 }
 
 // dsums[g][c] = (sum dn, sum dn * xhat), dn = dy * leaky'(n) * gamma;  dgamma += sum dy*leaky'*xhat, dbeta += sum dy*leaky'
-template <typename T>
-__global__ __launch_bounds__(GT) void norm_act_bwd_reduce_kernel(NormArgs A) {
-    __shared__ float red[GT][8];
+// (DROP, here and in the apply pass: dy stands for dy * m / (1 - rate), m regenerated from the forward's (seed, call))
+template <typename T, bool DROP>
+__device__ __forceinline__ void norm_act_bwd_reduce_body(const NormArgs A, const DropArgs D, float (*red)[8]) {
     const int lanes = A.c >> 2, cl = threadIdx.x % lanes, rl = threadIdx.x / lanes, rstep = GT / lanes;
     const int g = blockIdx.y, c4 = 4 * cl;
     f32x4 mean, rstd, ga, be;
@@ -259,12 +308,13 @@ __global__ __launch_bounds__(GT) void norm_act_bwd_reduce_kernel(NormArgs A) {
     long long r1 = r0 + A.rows_per_block;
     r1 = r1 < A.rows ? r1 : A.rows;
     const size_t base = ((size_t)g * A.rows) * A.c + c4;
+    const DropState<DROP> S(D);
     f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};   // sum d, sum d*xhat with d = dy*leaky'
 #pragma unroll 4
     for (long long r = r0 + rl; r < r1; r += rstep) {
         const size_t off = base + (size_t)r * A.c;
         const f32x4 v = ld4(static_cast<const T *>(A.x) + off);
-        const f32x4 d = ld4(static_cast<const T *>(A.dy) + off);
+        const f32x4 d = drop4<DROP>(ld4(static_cast<const T *>(A.dy) + off), D, S, off);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float xh = (v[i] - mean[i]) * rstd[i];
@@ -296,8 +346,8 @@ __global__ __launch_bounds__(GT) void norm_act_bwd_reduce_kernel(NormArgs A) {
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(GT) void norm_act_bwd_apply_kernel(NormArgs A) {
+template <typename T, bool DROP>
+__device__ __forceinline__ void norm_act_bwd_apply_body(const NormArgs A, const DropArgs D) {
     const int lanes = A.c >> 2, cl = threadIdx.x % lanes, rl = threadIdx.x / lanes, rstep = GT / lanes;
     const int g = blockIdx.y, c4 = 4 * cl;
     f32x4 mean, rstd, ga, be, m1, m2;
@@ -315,10 +365,11 @@ __global__ __launch_bounds__(GT) void norm_act_bwd_apply_kernel(NormArgs A) {
     r1 = r1 < A.rows ? r1 : A.rows;
     const size_t base = ((size_t)g * A.rows) * A.c + c4;
     unsigned vmax = 0;
+    const DropState<DROP> S(D);
     for (long long r = r0 + rl; r < r1; r += rstep) {
         const size_t off = base + (size_t)r * A.c;
         const f32x4 v = ld4(static_cast<const T *>(A.x) + off);
-        const f32x4 d = ld4(static_cast<const T *>(A.dy) + off);
+        const f32x4 d = drop4<DROP>(ld4(static_cast<const T *>(A.dy) + off), D, S, off);
         f32x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -331,6 +382,54 @@ __global__ __launch_bounds__(GT) void norm_act_bwd_apply_kernel(NormArgs A) {
         if constexpr (sizeof(T) == 4) vmax = amax_acc4(vmax, o);
     }
     if constexpr (sizeof(T) == 4) { if (A.amax) amax_commit(vmax, A.amax); }
+}
+
+// The kernels proper: the plain forms, and the dropout forms with the generator's state as a second argument
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act_fwd_kernel(NormArgs A) { norm_act_fwd_body<T, false>(A, DropArgs{}); }
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act_bwd_reduce_kernel(NormArgs A) {
+    __shared__ float red[GT][8];
+    norm_act_bwd_reduce_body<T, false>(A, DropArgs{}, red);
+}
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act_bwd_apply_kernel(NormArgs A) { norm_act_bwd_apply_body<T, false>(A, DropArgs{}); }
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act_dropout_fwd_kernel(NormArgs A, DropArgs D) { norm_act_fwd_body<T, true>(A, D); }
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act_dropout_bwd_reduce_kernel(NormArgs A, DropArgs D) {
+    __shared__ float red[GT][8];
+    norm_act_bwd_reduce_body<T, true>(A, D, red);
+}
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act_dropout_bwd_apply_kernel(NormArgs A, DropArgs D) {
+    norm_act_bwd_apply_body<T, true>(A, D);
+}
+
+// The mask itself, one byte per element (1 = kept): how the library reproduces the mask of a (seed, call) outside the norm
+// passes.  One thread per 4 consecutive elements, as there.
+__global__ __launch_bounds__(256) void dropout_mask_kernel(unsigned char *__restrict__ mask, long long numel, DropArgs D) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long e = 4 * q;
+    if (e >= numel) return;
+    const u32x4 w = philox4x32_10((unsigned long long)q, D.state[1], D.state[0]);
+    if (e + 4 <= numel) {
+        typedef unsigned char u8x4 __attribute__((ext_vector_type(4)));
+        *reinterpret_cast<u8x4 *>(mask + e) = u8x4{(unsigned char)(w.w[0] >= D.thresh), (unsigned char)(w.w[1] >= D.thresh),
+                                                  (unsigned char)(w.w[2] >= D.thresh), (unsigned char)(w.w[3] >= D.thresh)};
+    } else {
+        for (int i = 0; e + i < numel; ++i) mask[e + i] = (unsigned char)(w.w[i] >= D.thresh);
+    }
+}
+
+// saved = state, then call += 1: what a dropout forward does to the generator after its kernel has read it
+__global__ void dropout_state_next_kernel(long long *__restrict__ state, long long *__restrict__ saved) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const long long seed = state[0], call = state[1];
+        saved[0] = seed;
+        saved[1] = call;
+        state[1] = (long long)((unsigned long long)call + 1ull);
+    }
 }
 
 // ---- the tail of a separable block in ONE pass per direction:  y = leaky(norm_a(xa)) + leaky(norm_b(xb)),
@@ -569,9 +668,20 @@ static int chan_stats_any(const void *x_cl, int groups, long long rows, int c, f
     return 0;
 }
 
+// rate in (0, 1) and the device (seed, call) of a dropout entry point -> the kernels' DropArgs
+static int make_drop(double rate, const long long *state, DropArgs &D) {
+    if (!(rate > 0.0 && rate < 1.0)) return EPN_EINVAL;
+    if (!state) return EPN_ENULL;
+    const float p = (float)rate;
+    D.state = reinterpret_cast<const unsigned long long *>(state);
+    D.thresh = (unsigned)(unsigned long long)(rate * 4294967296.0);    // floor: rate < 1 keeps it below 2^32
+    D.scale = 1.0f / (1.0f - p);
+    return 0;
+}
+
 static int norm_act_fwd_any(const void *x_cl, int groups, long long rows, int c, const float *sums, const float *gamma,
                             const float *beta, const void *residual_cl, float eps, float slope, void *y_cl, int bf16,
-                            epn_stream_t stream) {
+                            epn_stream_t stream, const DropArgs *drop = nullptr) {
     int rc = check_norm(groups, rows, c);
     if (rc) return rc;
     if (groups == 0 || rows == 0) return 0;
@@ -579,7 +689,10 @@ static int norm_act_fwd_any(const void *x_cl, int groups, long long rows, int c,
     dim3 grid;
     NormArgs A = make_norm(rows, c, eps, slope, grid, groups);
     A.x = x_cl; A.sums = sums; A.gamma = gamma; A.beta = beta; A.res = residual_cl; A.y = y_cl;
-    if (bf16) EPN_LAUNCH(norm_act_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
+    if (drop) {
+        if (bf16) EPN_LAUNCH(norm_act_dropout_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
+        else EPN_LAUNCH(norm_act_dropout_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
+    } else if (bf16) EPN_LAUNCH(norm_act_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
     else EPN_LAUNCH(norm_act_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
     EPN_CHECK_LAUNCH();
     return 0;
@@ -588,7 +701,7 @@ static int norm_act_fwd_any(const void *x_cl, int groups, long long rows, int c,
 static int norm_act_bwd_reduce_any(const void *x_cl, const void *dy_cl, int groups, long long rows, int c,
                                    const float *sums, const float *gamma, const float *beta, float eps, float slope,
                                    float *dsums, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
-                                   int bf16, epn_stream_t stream) {
+                                   int bf16, epn_stream_t stream, const DropArgs *drop = nullptr) {
     int rc = check_norm(groups, rows, c);
     if (rc) return rc;
     if (!dsums) return EPN_ENULL;
@@ -605,7 +718,10 @@ static int norm_act_bwd_reduce_any(const void *x_cl, const void *dy_cl, int grou
     NormArgs A = make_norm(rows, c, eps, slope, grid, groups);
     A.x = x_cl; A.dy = dy_cl; A.sums = sums; A.gamma = gamma; A.beta = beta;
     A.out_sums = static_cast<float *>(workspace);
-    if (bf16) EPN_LAUNCH(norm_act_bwd_reduce_kernel<__bf16>, grid, dim3(GT), 0, st, A);
+    if (drop) {
+        if (bf16) EPN_LAUNCH(norm_act_dropout_bwd_reduce_kernel<__bf16>, grid, dim3(GT), 0, st, A, *drop);
+        else EPN_LAUNCH(norm_act_dropout_bwd_reduce_kernel<float>, grid, dim3(GT), 0, st, A, *drop);
+    } else if (bf16) EPN_LAUNCH(norm_act_bwd_reduce_kernel<__bf16>, grid, dim3(GT), 0, st, A);
     else EPN_LAUNCH(norm_act_bwd_reduce_kernel<float>, grid, dim3(GT), 0, st, A);
     EPN_CHECK_LAUNCH();
     if (groups > 1) {                        // several groups accumulate with atomics; one group stores
@@ -627,7 +743,8 @@ static int amax_prepare(float *amax, int bf16, hipStream_t st) {
 
 static int norm_act_bwd_apply_any(const void *x_cl, const void *dy_cl, int groups, long long rows, int c,
                                   const float *sums, const float *dsums, const float *gamma, const float *beta, float eps,
-                                  float slope, void *dx_cl, int bf16, epn_stream_t stream, float *amax = nullptr) {
+                                  float slope, void *dx_cl, int bf16, epn_stream_t stream, float *amax = nullptr,
+                                  const DropArgs *drop = nullptr) {
     int rc = check_norm(groups, rows, c);
     if (rc) return rc;
     rc = amax_prepare(amax, bf16, epn_stream(stream));
@@ -638,7 +755,10 @@ static int norm_act_bwd_apply_any(const void *x_cl, const void *dy_cl, int group
     NormArgs A = make_norm(rows, c, eps, slope, grid, groups);
     A.x = x_cl; A.dy = dy_cl; A.sums = sums; A.dsums = dsums; A.gamma = gamma; A.beta = beta; A.y = dx_cl;
     A.amax = reinterpret_cast<unsigned *>(amax);
-    if (bf16) EPN_LAUNCH(norm_act_bwd_apply_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
+    if (drop) {
+        if (bf16) EPN_LAUNCH(norm_act_dropout_bwd_apply_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
+        else EPN_LAUNCH(norm_act_dropout_bwd_apply_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
+    } else if (bf16) EPN_LAUNCH(norm_act_bwd_apply_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
     else EPN_LAUNCH(norm_act_bwd_apply_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
     EPN_CHECK_LAUNCH();
     return 0;
@@ -906,6 +1026,83 @@ extern "C" int epn_norm_act_bwd_apply_bf16(const void *x_cl, const void *dy_cl, 
                                            const float *sums, const float *dsums, const float *gamma, const float *beta,
                                            float eps, float slope, void *dx_cl, epn_stream_t stream) {
     return norm_act_bwd_apply_any(x_cl, dy_cl, groups, rows, c, sums, dsums, gamma, beta, eps, slope, dx_cl, 1, stream);
+}
+
+// ---- dropout forms (include/epn_so3conv.h "dropout inside the norm passes"): rate in (0, 1), state = device (seed, call)
+extern "C" int epn_norm_act_dropout_fwd_f32(const float *x_cl, int groups, long long rows, int c, const float *sums,
+                                            const float *gamma, const float *beta, const float *residual_cl, float eps,
+                                            float slope, double rate, const long long *state, float *y_cl,
+                                            epn_stream_t stream) {
+    DropArgs D;
+    if (const int rc = make_drop(rate, state, D)) return rc;
+    return norm_act_fwd_any(x_cl, groups, rows, c, sums, gamma, beta, residual_cl, eps, slope, y_cl, 0, stream, &D);
+}
+extern "C" int epn_norm_act_dropout_fwd_bf16(const void *x_cl, int groups, long long rows, int c, const float *sums,
+                                             const float *gamma, const float *beta, const void *residual_cl, float eps,
+                                             float slope, double rate, const long long *state, void *y_cl,
+                                             epn_stream_t stream) {
+    DropArgs D;
+    if (const int rc = make_drop(rate, state, D)) return rc;
+    return norm_act_fwd_any(x_cl, groups, rows, c, sums, gamma, beta, residual_cl, eps, slope, y_cl, 1, stream, &D);
+}
+extern "C" int epn_norm_act_dropout_bwd_reduce_f32(const float *x_cl, const float *dy_cl, int groups, long long rows, int c,
+                                                   const float *sums, const float *gamma, const float *beta, float eps,
+                                                   float slope, double rate, const long long *state, float *dsums,
+                                                   float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                                   epn_stream_t stream) {
+    DropArgs D;
+    if (const int rc = make_drop(rate, state, D)) return rc;
+    return norm_act_bwd_reduce_any(x_cl, dy_cl, groups, rows, c, sums, gamma, beta, eps, slope, dsums, dgamma, dbeta,
+                                   workspace, workspace_bytes, 0, stream, &D);
+}
+extern "C" int epn_norm_act_dropout_bwd_reduce_bf16(const void *x_cl, const void *dy_cl, int groups, long long rows, int c,
+                                                    const float *sums, const float *gamma, const float *beta, float eps,
+                                                    float slope, double rate, const long long *state, float *dsums,
+                                                    float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                                    epn_stream_t stream) {
+    DropArgs D;
+    if (const int rc = make_drop(rate, state, D)) return rc;
+    return norm_act_bwd_reduce_any(x_cl, dy_cl, groups, rows, c, sums, gamma, beta, eps, slope, dsums, dgamma, dbeta,
+                                   workspace, workspace_bytes, 1, stream, &D);
+}
+extern "C" int epn_norm_act_dropout_bwd_apply_f32(const float *x_cl, const float *dy_cl, int groups, long long rows, int c,
+                                                  const float *sums, const float *dsums, const float *gamma,
+                                                  const float *beta, float eps, float slope, double rate,
+                                                  const long long *state, float *dx_cl, epn_stream_t stream) {
+    DropArgs D;
+    if (const int rc = make_drop(rate, state, D)) return rc;
+    return norm_act_bwd_apply_any(x_cl, dy_cl, groups, rows, c, sums, dsums, gamma, beta, eps, slope, dx_cl, 0, stream,
+                                  nullptr, &D);
+}
+extern "C" int epn_norm_act_dropout_bwd_apply_bf16(const void *x_cl, const void *dy_cl, int groups, long long rows, int c,
+                                                   const float *sums, const float *dsums, const float *gamma,
+                                                   const float *beta, float eps, float slope, double rate,
+                                                   const long long *state, void *dx_cl, epn_stream_t stream) {
+    DropArgs D;
+    if (const int rc = make_drop(rate, state, D)) return rc;
+    return norm_act_bwd_apply_any(x_cl, dy_cl, groups, rows, c, sums, dsums, gamma, beta, eps, slope, dx_cl, 1, stream,
+                                  nullptr, &D);
+}
+
+extern "C" int epn_dropout_mask_u8(unsigned char *mask, long long numel, double rate, const long long *state,
+                                   epn_stream_t stream) {
+    if (numel < 0 || numel > (1LL << 40)) return EPN_EINVAL;
+    DropArgs D;
+    if (const int rc = make_drop(rate, state, D)) return rc;
+    if (numel == 0) return 0;
+    if (!mask) return EPN_ENULL;
+    if ((uintptr_t)mask % 4) return EPN_EINVAL;
+    const long long quads = (numel + 3) / 4;
+    EPN_LAUNCH(dropout_mask_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, epn_stream(stream), mask, numel, D);
+    EPN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int epn_dropout_state_next(long long *state, long long *saved, epn_stream_t stream) {
+    if (!state || !saved) return EPN_ENULL;
+    EPN_LAUNCH(dropout_state_next_kernel, dim3(1), dim3(64), 0, epn_stream(stream), state, saved);
+    EPN_CHECK_LAUNCH();
+    return 0;
 }
 
 // ---- IntraSO3Conv grouping as a tensor (the "split" form): grouped[col][k*c + ci] = x[(pt*na + idx[a][k])*c + ci].

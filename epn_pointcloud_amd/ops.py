@@ -1315,6 +1315,113 @@ class NormActFn(torch.autograd.Function):
         return dx, dg, db, (dy if has_res else None), dcb, None, None, None
 
 
+# ---- dropout inside the norm passes: generator state, mask, Function ------------------------------------------------
+_DROPOUT_STATE = {}      # device index -> int64[2] device tensor (seed, call)
+
+
+def _as_int64(v):
+    """A Python int (torch seeds go up to 2^64 - 1) as the int64 with the same 64 bits."""
+    v = int(v) & (2 ** 64 - 1)
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def _device_index(device):
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RuntimeError("the dropout generator state lives on a CUDA device")
+    return torch.cuda.current_device() if device.index is None else device.index
+
+
+def dropout_state(device=None):
+    """The device's dropout generator state: an int64[2] DEVICE tensor (seed, call), created from torch.initial_seed() on
+    first use.  The kernels read it through its pointer and every dropout forward advances `call` on the device, so a
+    captured graph draws a fresh mask on each replay.  Clone it to remember a (seed, call) (see dropout_mask)."""
+    i = _device_index(device)
+    st = _DROPOUT_STATE.get(i)
+    if st is None:
+        st = _DROPOUT_STATE[i] = torch.tensor([_as_int64(torch.initial_seed()), 0], dtype=torch.int64,
+                                              device=torch.device("cuda", i))
+    return st
+
+
+def seed_dropout(seed, device=None):
+    """Reset the device's dropout generator state to (seed, 0), in place (captured graphs keep pointing at it)."""
+    st = dropout_state(device)
+    st.copy_(torch.tensor([_as_int64(seed), 0], dtype=torch.int64))
+    return st
+
+
+def dropout_mask(b, c, p, a, rate, state):
+    """The mask a dropout norm_act on a [b, c, p, a] tensor draws from `state`: logical [b, c, p, a] bool tensor in
+    channels-last memory, True = kept (include/epn_so3conv.h states the generator).  state: an int64[2] device tensor
+    (seed, call) -- e.g. dropout_state(device).clone() taken before the call -- or a (seed, call) pair of ints (current
+    device)."""
+    rate = _check_rate(rate)
+    if not torch.is_tensor(state):
+        seed, call = state
+        state = torch.tensor([_as_int64(seed), _as_int64(call)], dtype=torch.int64, device=torch.device("cuda", _device_index(None)))
+    if state.dtype != torch.int64 or state.numel() != 2:
+        raise TypeError("state must be an int64[2] tensor (seed, call)")
+    m = torch.empty((b, c, p, a), dtype=torch.uint8, device=state.device, memory_format=torch.channels_last)
+    _lib.check(_lib.get_lib().epn_dropout_mask_u8(ctypes.c_void_p(m.data_ptr()), m.numel(), rate,
+                                                  _lib.dev_ptr(state, "state", torch.int64), _lib.stream_of(m)), "dropout_mask")
+    return m.view(torch.bool)
+
+
+def _check_rate(rate):
+    rate = float(rate)
+    if not 0.0 < rate < 1.0:
+        raise ValueError(f"dropout rate must satisfy 0 < rate < 1, got {rate}")
+    return rate
+
+
+class NormActDropoutFn(torch.autograd.Function):
+    """y = dropout(leaky_relu(norm(x)), rate) (+ residual, added after the mask) -- `self.dropout(relu(norm(x)))` of
+    SPConvNets/utils/base_so3conv.py:58-59 / 124-125, the skip branch of :205-211 -- in the same two streaming passes per
+    direction as NormActFn: the mask is generated in the kernels from the device's (seed, call) (dropout_state) and
+    regenerated, not stored, by the backward.  The forward keeps a copy of (seed, call) for its backward and advances `call`
+    on the device.  y leaves WITHOUT a max|y| tag (two-piece fp16 GEMMs scan it: it is 1 / (1 - rate) above the undropped
+    tensor).  Returns (y, sums) like NormActFn."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, conv_bias, instance, eps, slope, rate, state):
+        ctx.set_materialize_grads(False)
+        lib = _lib.get_lib()
+        xc = to_cl(x, "x")
+        b, c, p, a = xc.shape
+        groups, rows = (b, p * a) if instance else (1, b * p * a)
+        st = _lib.stream_of(xc)
+        dt = xc.dtype
+        sums = _chan_stats(xc, groups, rows, c)
+        y = empty_cl(b, c, p, a, xc.device, dt)
+        g = gamma.contiguous() if gamma is not None else None
+        bt = beta.contiguous() if beta is not None else None
+        r = cast_feats(to_cl(residual, "residual"), dt) if residual is not None else None
+        sp = _lib.dev_ptr(state, "dropout state", torch.int64)
+        _lib.check(_entry(lib, "norm_act_dropout_fwd", dt)(_cl_ptr(xc), groups, rows, c, _lib.dev_ptr(sums, "sums"),
+                                                           _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"),
+                                                           _cl_ptr(r) if r is not None else ctypes.c_void_p(0), float(eps),
+                                                           float(slope), rate, sp, _cl_ptr(y), st), "norm_act_dropout_fwd")
+        saved = torch.empty_like(state)
+        _lib.check(lib.epn_dropout_state_next(sp, _lib.dev_ptr(saved, "saved state", torch.int64), st), "dropout_state_next")
+        ctx.save_for_backward(xc, sums, g, bt, saved)
+        ctx.cfg = (groups, rows, c, float(eps), float(slope), residual is not None, conv_bias is not None, rate)
+        ctx.mark_non_differentiable(sums)
+        return y, sums
+
+    @staticmethod
+    def backward(ctx, grad_y, _grad_sums):
+        if grad_y is None:
+            return (None,) * 10
+        xc, sums, g, bt, saved = ctx.saved_tensors
+        groups, rows, c, eps, slope, has_res, has_cb, rate = ctx.cfg
+        dy = cast_feats(to_cl(grad_y, "grad_y"), xc.dtype)
+        dx, dg, db = _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, ctx.needs_input_grad[0],
+                                        drop=(rate, saved))
+        dcb = torch.zeros(c, dtype=torch.float32, device=xc.device) if has_cb else None
+        return dx, dg, db, (dy if has_res else None), dcb, None, None, None, None, None      # the residual is never masked
+
+
 def _pair_side(sums, g, bt, eps, instance):
     sd = _lib.NormPairSide()
     sd.sums = _lib.dev_ptr(sums, "sums")
@@ -1456,25 +1563,30 @@ def _stats(xc, groups, rows, c, part=None, block_rows=32):
     return sums if sums is not None else _chan_stats(xc, groups, rows, c)
 
 
-def _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, need_dx):
-    """Backward of y = leaky(norm(x)): (dx, dgamma, dbeta) from x, dy and the forward statistics (two streaming passes)."""
+def _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, need_dx, drop=None):
+    """Backward of y = leaky(norm(x)): (dx, dgamma, dbeta) from x, dy and the forward statistics (two streaming passes).
+    drop = (rate, saved state) of a dropout forward: both passes regenerate its mask and read dy * m / (1 - rate) for dy."""
     lib = _lib.get_lib()
     st = _lib.stream_of(xc)
+    reduce_name, apply_name, extra = "norm_act_bwd_reduce", "norm_act_bwd_apply", ()
+    if drop is not None:
+        reduce_name, apply_name = "norm_act_dropout_bwd_reduce", "norm_act_dropout_bwd_apply"
+        extra = (float(drop[0]), _lib.dev_ptr(drop[1], "dropout state", torch.int64))
     dsums = torch.empty_like(sums)
     dg = torch.empty(c, dtype=torch.float32, device=xc.device) if g is not None else None
     db = torch.empty(c, dtype=torch.float32, device=xc.device) if bt is not None else None
     gp, bp = _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta")
     ws, wsp, wsn = _ws(lib.epn_norm_workspace_bytes(groups, rows, c), xc.device)
-    _lib.check(_entry(lib, "norm_act_bwd_reduce", xc.dtype)(_cl_ptr(xc), _cl_ptr(dy), groups, rows, c,
-                                               _lib.dev_ptr(sums, "sums"), gp, bp, eps, slope,
+    _lib.check(_entry(lib, reduce_name, xc.dtype)(_cl_ptr(xc), _cl_ptr(dy), groups, rows, c,
+                                               _lib.dev_ptr(sums, "sums"), gp, bp, eps, slope, *extra,
                                                _lib.dev_ptr(dsums, "dsums"), _lib.dev_ptr(dg, "dgamma"),
-                                               _lib.dev_ptr(db, "dbeta"), wsp, wsn, st), "norm_act_bwd_reduce")
+                                               _lib.dev_ptr(db, "dbeta"), wsp, wsn, st), reduce_name)
     dx = None
     if need_dx:
         dx = torch.empty_like(xc)
-        _lib.check(_entry(lib, "norm_act_bwd_apply", xc.dtype)(_cl_ptr(xc), _cl_ptr(dy), groups, rows, c,
+        _lib.check(_entry(lib, apply_name, xc.dtype)(_cl_ptr(xc), _cl_ptr(dy), groups, rows, c,
                                                   _lib.dev_ptr(sums, "sums"), _lib.dev_ptr(dsums, "dsums"), gp, bp,
-                                                  eps, slope, _cl_ptr(dx), st), "norm_act_bwd_apply")
+                                                  eps, slope, *extra, _cl_ptr(dx), st), apply_name)
     return dx, dg, db
 
 
@@ -1593,17 +1705,23 @@ def _update_running_stats(norm, sums, n, conv_bias=None):
             norm.running_var.lerp_(var, m)
 
 
-def norm_act(x, norm, residual=None, slope=0.01, conv_bias=None):
+def norm_act(x, norm, residual=None, slope=0.01, conv_bias=None, *, dropout=0.0):
     """leaky_relu(norm(x)) (+ residual) with `norm` an nn.BatchNorm2d or nn.InstanceNorm2d(affine=False) module whose
     parameters / running statistics are used and updated exactly as the module would (training mode).
     conv_bias: per-channel bias of the convolution that produced x, NOT yet added to x.  Both norms subtract the
     per-channel mean, so norm(x + b) == norm(x) and d/db == 0 exactly: the add (a full read + write of the tensor) and
-    the bias-gradient reduction are skipped, only BatchNorm's running_mean needs b."""
+    the bias-gradient reduction are skipped, only BatchNorm's running_mean needs b.
+    dropout (keyword only): rate of an nn.Dropout applied to leaky_relu(norm(x)) BEFORE the residual is added, 0 < rate < 1 (or 0.0: none),
+    drawn from dropout_state(x.device) inside the same passes (NormActDropoutFn); the running statistics are those of x."""
     import torch.nn as nn
     instance = isinstance(norm, nn.InstanceNorm2d)
     gamma = getattr(norm, "weight", None)
     beta = getattr(norm, "bias", None)
-    y, sums = NormActFn.apply(x, gamma, beta, residual, conv_bias, instance, norm.eps, slope)
+    if dropout == 0.0:
+        y, sums = NormActFn.apply(x, gamma, beta, residual, conv_bias, instance, norm.eps, slope)
+    else:
+        y, sums = NormActDropoutFn.apply(x, gamma, beta, residual, conv_bias, instance, norm.eps, slope,
+                                         _check_rate(dropout), dropout_state(x.device))
     _update_running_stats(norm, sums, x.shape[0] * x.shape[2] * x.shape[3], conv_bias)
     return y
 

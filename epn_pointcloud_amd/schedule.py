@@ -90,6 +90,15 @@ class _ConvNorm(nn.Module):
         self.norm = norm
 
 
+def _hip_dropout_rate(dropout):
+    """Rate the HIP norm passes apply themselves for a block's `dropout` module (ops.norm_act(..., dropout=rate)): 0.0 without
+    dropout, the module's rate for 0 < rate < 1, None when the block has to take the stock modules (rate 1, or the A/B
+    switch EPN_FUSED_DROPOUT=0: the behaviour before the dropout kernels existed)."""
+    if dropout is None:
+        return 0.0
+    return dropout.p if 0.0 < dropout.p < 1.0 and ab("EPN_FUSED_DROPOUT") == "1" else None
+
+
 class SeparableBlock(nn.Module):
     """One SeparableSO3ConvBlock (SPConvNets/utils/base_so3conv.py:168-212) with the reference's module tree, so a
     reference checkpoint's keys (`inter_conv.conv.basic_conv.W`, `inter_conv.norm.*`, `intra_conv.conv.*`,
@@ -138,11 +147,15 @@ class FusedSeparableBlock(SeparableBlock):
     """Same module tree / state_dict as SeparableBlock, with the glue on the HIP "block glue" kernels:
     norm + leaky_relu (+ the residual add) are two streaming passes each, the 1x1 skip convolution runs on the intra
     GEMM kernel (one anchor "neighbour", identity index) -- everything stays channels-last, no layout copies.
-    Training-mode semantics (batch statistics); eval mode and dropout fall back to the stock modules."""
+    Training-mode semantics (batch statistics); eval mode falls back to the stock modules.  With dropout_rate in (0, 1) the
+    block stays here: both main-branch norms draw their mask inside their own passes (ops.norm_act(..., dropout=rate), the
+    skip branch is added unmasked as in base_so3conv.py:205-211) in the plain forms -- the norm-on-load and pair forms do not
+    take dropout yet; a rate of 1 takes the stock modules."""
 
     def forward(self, x, inter_idx=None, inter_w=None):
         c_out = self.inter_conv.conv.dim_out
-        if (not self.training) or self.dropout is not None or not ops.norm_act_supported(c_out) or not self.use_intra:
+        drop = _hip_dropout_rate(self.dropout)
+        if (not self.training) or drop is None or not ops.norm_act_supported(c_out) or not self.use_intra:
             return super().forward(x, inter_idx, inter_w)
         import os
         conv = self.inter_conv.conv
@@ -167,7 +180,7 @@ class FusedSeparableBlock(SeparableBlock):
         y_part = conv.__dict__.pop("_out_stats", None)
         y_part = y_part if epi else None
 
-        pair = ab("EPN_NORM_PAIR") == "1"     # skip norm folded into the block's final pass
+        pair = ab("EPN_NORM_PAIR") == "1" and not drop    # skip norm folded into the block's final pass
 
         def skip_branch():
             sk = skip
@@ -187,7 +200,7 @@ class FusedSeparableBlock(SeparableBlock):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 s, s_part = skip_branch()
-        if ab("EPN_NORM_ON_LOAD") == "1" and self.intra_conv.conv.takes_spectral_form(y.feats.is_cuda):
+        if not drop and ab("EPN_NORM_ON_LOAD") == "1" and self.intra_conv.conv.takes_spectral_form(y.feats.is_cuda):
             # norm + leaky_relu of the inter convolution applied as the intra convolution's basis change loads its
             # rows: the normalised tensor is never written
             iconv = self.intra_conv.conv
@@ -198,7 +211,7 @@ class FusedSeparableBlock(SeparableBlock):
                 iconv.want_out_stats = False
             z_part = iconv.__dict__.pop("_out_stats", None)
         else:
-            feat = ops.norm_act(y.feats, self.inter_conv.norm)
+            feat = ops.norm_act(y.feats, self.inter_conv.norm, dropout=drop)
             z = self.intra_conv.conv(zptk.SphericalPointCloud(y.xyz, feat, y.anchors))
             z_part = None
         if side is None:
@@ -214,7 +227,8 @@ class FusedSeparableBlock(SeparableBlock):
             out = ops.norm_act_pair(z.feats, self.intra_conv.norm, s, self.norm, conv_bias_b=self.skip_conv.bias,
                                     part_b=s_part, part_a=z_part)
         else:
-            out = ops.norm_act(z.feats, self.intra_conv.norm, residual=s)   # leaky(IN(z)) + skip in the same pass
+            # leaky(IN(z)) (masked when the block has dropout) + skip in the same pass
+            out = ops.norm_act(z.feats, self.intra_conv.norm, residual=s, dropout=drop)
         return inter_idx, inter_w, sample_idx, zptk.SphericalPointCloud(z.xyz, out, z.anchors)
 
 
@@ -233,8 +247,9 @@ class InterBlock(nn.Module):
 
     def forward(self, x, inter_idx=None, inter_w=None):
         inter_idx, inter_w, sample_idx, y = self.conv(x, inter_idx, inter_w)
-        if self.training and self.dropout is None and y.feats.is_cuda and ops.norm_act_supported(y.feats.shape[1]):
-            feat = ops.norm_act(y.feats, self.norm)
+        drop = _hip_dropout_rate(self.dropout)
+        if self.training and drop is not None and y.feats.is_cuda and ops.norm_act_supported(y.feats.shape[1]):
+            feat = ops.norm_act(y.feats, self.norm, dropout=drop)
         else:
             feat = F.leaky_relu(self.norm(y.feats))
             if self.training and self.dropout is not None:

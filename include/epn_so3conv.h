@@ -266,6 +266,49 @@ int epn_norm_act_bwd_apply_amax_f32(const float *x_cl, const float *dy_cl, int g
                                     const float *sums, const float *dsums, const float *gamma, const float *beta, float eps,
                                     float slope, float *dx_cl, float *dx_amax, epn_stream_t stream);
 
+/* Dropout inside the norm passes: the nn.Dropout that follows norm + leaky_relu in every block of the reference
+ * (SPConvNets/utils/base_so3conv.py:58-59 / 124-125; the separable block adds its skip branch after it, :205-211), as one
+ * more multiply in passes that already stream the tensor.  The mask is not stored: it is a function of
+ * (seed, call, e, rate) alone, e = the element's flat offset in the channels-last tensor (for logical [b][c][p][a]:
+ * e = ((b_i*p + p_i)*a + a_i)*c + ch).  Element e is DROPPED iff
+ *   Philox4x32-10(counter = {lo32(e>>2), hi32(e>>2), lo32(call), hi32(call)}, key = {lo32(seed), hi32(seed)})[e & 3]
+ *       < floor(rate * 2^32)
+ * (Salmon et al., SC'11: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, 10 rounds), kept
+ * elements are scaled by 1 / (1 - rate) (one fp32 division).  0 < rate < 1, else EPN_EINVAL.
+ * state: DEVICE int64[2] = (seed, call), read by the kernels -- nothing of it is a launch argument, so a captured graph
+ * draws a new mask on every replay.  epn_dropout_state_next copies state to `saved` (what the backward entry points of
+ * that forward take as their `state`) and adds 1 to call.
+ *   fwd       : y = m * leaky(norm(x)) / (1 - rate) (+ residual: added after the mask, never masked)
+ *   bwd_reduce, bwd_apply: as the plain entry points with dy * m / (1 - rate) in place of dy (m regenerated); the
+ *               residual's gradient is the caller's dy itself.
+ * epn_dropout_mask_u8 writes the mask of `numel` elements from offset 0, one byte each, 1 = kept (mask 4-byte aligned). */
+int epn_norm_act_dropout_fwd_f32(const float *x_cl, int groups, long long rows, int c, const float *sums,
+                                 const float *gamma, const float *beta, const float *residual_cl, float eps, float slope,
+                                 double rate, const long long *state, float *y_cl, epn_stream_t stream);
+int epn_norm_act_dropout_bwd_reduce_f32(const float *x_cl, const float *dy_cl, int groups, long long rows, int c,
+                                        const float *sums, const float *gamma, const float *beta, float eps, float slope,
+                                        double rate, const long long *state, float *dsums, float *dgamma, float *dbeta,
+                                        void *workspace, size_t workspace_bytes, epn_stream_t stream);
+int epn_norm_act_dropout_bwd_apply_f32(const float *x_cl, const float *dy_cl, int groups, long long rows, int c,
+                                       const float *sums, const float *dsums, const float *gamma, const float *beta,
+                                       float eps, float slope, double rate, const long long *state, float *dx_cl,
+                                       epn_stream_t stream);
+/* bf16 features (x / y / dy / dx / residual are __bf16; statistics, parameters and arithmetic fp32), same reference lines
+ * (base_so3conv.py:58-59 / 124-125) */
+int epn_norm_act_dropout_fwd_bf16(const void *x_cl, int groups, long long rows, int c, const float *sums,
+                                  const float *gamma, const float *beta, const void *residual_cl, float eps, float slope,
+                                  double rate, const long long *state, void *y_cl, epn_stream_t stream);
+int epn_norm_act_dropout_bwd_reduce_bf16(const void *x_cl, const void *dy_cl, int groups, long long rows, int c,
+                                         const float *sums, const float *gamma, const float *beta, float eps, float slope,
+                                         double rate, const long long *state, float *dsums, float *dgamma, float *dbeta,
+                                         void *workspace, size_t workspace_bytes, epn_stream_t stream);
+int epn_norm_act_dropout_bwd_apply_bf16(const void *x_cl, const void *dy_cl, int groups, long long rows, int c,
+                                        const float *sums, const float *dsums, const float *gamma, const float *beta,
+                                        float eps, float slope, double rate, const long long *state, void *dx_cl,
+                                        epn_stream_t stream);
+int epn_dropout_mask_u8(unsigned char *mask, long long numel, double rate, const long long *state, epn_stream_t stream);
+int epn_dropout_state_next(long long *state, long long *saved, epn_stream_t stream);
+
 /* replaces vgtk.cuda.grouping.initial_anchor_query (vgtk/vgtk/cuda/grouping_cuda.cpp:138-158, kernel
  * grouping_cuda_kernel.cu:116-167; only consumer: KernelPropagation, vgtk/vgtk/so3conv/modules.py:57-119).
  *   centers f32[b][3][nc]   xyz f32[m][3] (fragment points, shared by the batch)   kernel_points f32[ks][na][3]
