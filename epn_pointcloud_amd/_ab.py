@@ -18,6 +18,7 @@ AB_DEFAULTS = {
     "EPN_NORM_ON_LOAD": "1",         # first norm + leaky_relu applied as the basis change loads its rows
     "EPN_NORM_BWD_EPILOGUE": "1",    # first norm's backward sums from the inverse basis change's epilogue
     "EPN_FUSED_DROPOUT": "1",        # dropout_rate in (0, 1): masks drawn inside the HIP norm passes | "0": stock modules
+    "EPN_FUSED_EVAL": "1",           # eval() under no_grad: block glue on the frozen-statistics HIP passes | "0": stock modules
     "EPN_SPECTRAL_WEIGHTS": "fused", # spectral weights by one kernel | "torch"
     "EPN_C1_SAVE": "1",              # first layer keeps its grouped values for the weight gradient
     "EPN_C1_DW": "gemm",             # ... and computes it as a library TN GEMM | "kernel"

@@ -54,6 +54,8 @@ EXPORTS = [
     "epn_norm_act_dropout_fwd_f32", "epn_norm_act_dropout_bwd_reduce_f32", "epn_norm_act_dropout_bwd_apply_f32",
     "epn_norm_act_dropout_fwd_bf16", "epn_norm_act_dropout_bwd_reduce_bf16", "epn_norm_act_dropout_bwd_apply_bf16",
     "epn_dropout_mask_u8", "epn_dropout_state_next",
+    "epn_bn_frozen_stats_f32", "epn_norm_act_frozen_fwd_f32", "epn_norm_act_frozen_fwd_bf16", "epn_norm_act_pair_frozen_fwd",
+    "epn_so3_basis_norm_frozen_f32", "epn_so3_basis_norm_frozen_split_f32", "epn_so3_basis_norm_frozen_bf16",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -69,6 +71,11 @@ class InterDesc(ctypes.Structure):
 class NormPairSide(ctypes.Structure):
     """struct epn_norm_pair_side (include/epn_so3conv.h)."""
     _fields_ = [("sums", _vp), ("gamma", _vp), ("beta", _vp), ("eps", _cf), ("instance", _ci)]
+
+
+class NormPairFrozenSide(ctypes.Structure):
+    """struct epn_norm_pair_frozen_side (include/epn_so3conv.h)."""
+    _fields_ = [("stats", _vp), ("gamma", _vp), ("beta", _vp), ("eps", _cf), ("frozen", _ci)]
 
 
 class GemmNtProblem(ctypes.Structure):
@@ -292,6 +299,14 @@ def get_lib():
     lib.epn_dropout_mask_u8.argtypes = [_vp, _ll, _cd, _vp, _vp]
     lib.epn_dropout_state_next.argtypes = [_vp, _vp, _vp]
     lib.epn_dropout_mask_u8.restype = lib.epn_dropout_state_next.restype = _ci
+    # frozen statistics (eval mode): stats[c][2] in place of (sums, groups); forward only
+    lib.epn_bn_frozen_stats_f32.argtypes = [_vp, _vp, _vp, _ci, _vp, _vp]
+    lib.epn_norm_act_frozen_fwd_f32.argtypes = [_vp, _ll, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _vp, _vp]
+    lib.epn_norm_act_frozen_fwd_bf16.argtypes = lib.epn_norm_act_frozen_fwd_f32.argtypes
+    lib.epn_norm_act_pair_frozen_fwd.argtypes = [_vp, _vp, _ci, _ll, _ci, sp, ctypes.POINTER(NormPairFrozenSide), _cf, _vp, _ci, _vp]
+    lib.epn_norm_act_pair_frozen_fwd.restype = _ci
+    for _n in ("epn_so3_basis_norm_frozen_f32", "epn_so3_basis_norm_frozen_split_f32", "epn_so3_basis_norm_frozen_bf16"):
+        getattr(lib, _n).argtypes = [_vp, _vp, _vp, _ll, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

@@ -62,8 +62,20 @@ __device__ __forceinline__ void load_param4(const float *p, int c4, f32x4 &v, fl
     v = p ? *reinterpret_cast<const f32x4 *>(p + c4) : f32x4{dflt, dflt, dflt, dflt};
 }
 
-// mean / rstd of this thread's 4 channels from sums[g][c][2]
+// mean / rstd of this thread's 4 channels from sums[g][c][2];  FROZEN: sums is stats[c][2] = (mean, var) as they are
+// (epn_bn_frozen_stats_f32: an eval-mode BatchNorm's running statistics, one group) -- never (s1, s2) synthesised from them:
+// s2 / rows - mean^2 cancels when mean^2 >> var
+template <bool FROZEN = false>
 __device__ __forceinline__ void stats4(const NormArgs &A, int g, int c4, f32x4 &mean, f32x4 &rstd) {
+    if constexpr (FROZEN) {
+        const float *s = A.sums + (size_t)c4 * 2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            mean[i] = s[2 * i];
+            rstd[i] = rsqrtf(s[2 * i + 1] + A.eps);
+        }
+        return;
+    }
     const float *s = A.sums + ((size_t)g * A.c + c4) * 2;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -262,12 +274,12 @@ __device__ __forceinline__ f32x4 drop4(const f32x4 v, const DropArgs &D, const D
     return o;
 }
 
-template <typename T, bool DROP>
+template <typename T, bool DROP, bool FROZEN = false>
 __device__ __forceinline__ void norm_act_fwd_body(const NormArgs A, const DropArgs D) {
     const int lanes = A.c >> 2, cl = threadIdx.x % lanes, rl = threadIdx.x / lanes, rstep = GT / lanes;
     const int g = blockIdx.y, c4 = 4 * cl;
     f32x4 mean, rstd, ga, be;
-    stats4(A, g, c4, mean, rstd);
+    stats4<FROZEN>(A, g, c4, mean, rstd);
     load_param4(A.gamma, c4, ga, 1.0f);
     load_param4(A.beta, c4, be, 0.0f);
     const long long r0 = (long long)blockIdx.x * A.rows_per_block;
@@ -396,6 +408,9 @@ template <typename T>
 __global__ __launch_bounds__(GT) void norm_act_bwd_apply_kernel(NormArgs A) { norm_act_bwd_apply_body<T, false>(A, DropArgs{}); }
 template <typename T>
 __global__ __launch_bounds__(GT) void norm_act_dropout_fwd_kernel(NormArgs A, DropArgs D) { norm_act_fwd_body<T, true>(A, D); }
+// the frozen form (eval-mode BatchNorm2d): A.sums = stats[c][2] = (mean, var), one group
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act_frozen_fwd_kernel(NormArgs A) { norm_act_fwd_body<T, false, true>(A, DropArgs{}); }
 template <typename T>
 __global__ __launch_bounds__(GT) void norm_act_dropout_bwd_reduce_kernel(NormArgs A, DropArgs D) {
     __shared__ float red[GT][8];
@@ -455,7 +470,18 @@ struct NormArgs2 {
     unsigned *amax;       // optional (fp32): max |y| (fwd) / max |dx of side b| (bwd_apply): see NormArgs::amax
 };
 
+// FROZEN: S.sums is stats[c][2] = (mean, var) of an eval-mode BatchNorm2d (see stats4)
+template <bool FROZEN = false>
 __device__ __forceinline__ void side_stats4(const NormSide &S, int c, int g, int c4, f32x4 &mean, f32x4 &rstd) {
+    if constexpr (FROZEN) {
+        const float *s = S.sums + (size_t)c4 * 2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            mean[i] = s[2 * i];
+            rstd[i] = rsqrtf(s[2 * i + 1] + S.eps);
+        }
+        return;
+    }
     const float *s = S.sums + ((size_t)(S.per_cloud ? g : 0) * c + c4) * 2;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -466,13 +492,14 @@ __device__ __forceinline__ void side_stats4(const NormSide &S, int c, int g, int
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(GT) void norm_act2_fwd_kernel(NormArgs2 A) {
+// FROZEN_B: side b normalises with frozen statistics (side a: instance / batch statistics from its sums, as ever)
+template <typename T, bool FROZEN_B>
+__device__ __forceinline__ void norm_act2_fwd_body(const NormArgs2 A) {
     const int lanes = A.c >> 2, cl = threadIdx.x % lanes, rl = threadIdx.x / lanes, rstep = GT / lanes;
     const int g = blockIdx.y, c4 = 4 * cl;
     f32x4 ma, ra, ga, ba, mb, rb, gb, bb;
     side_stats4(A.a, A.c, g, c4, ma, ra);
-    side_stats4(A.b, A.c, g, c4, mb, rb);
+    side_stats4<FROZEN_B>(A.b, A.c, g, c4, mb, rb);
     load_param4(A.a.gamma, c4, ga, 1.0f); load_param4(A.a.beta, c4, ba, 0.0f);
     load_param4(A.b.gamma, c4, gb, 1.0f); load_param4(A.b.beta, c4, bb, 0.0f);
     const long long r0 = (long long)blockIdx.x * A.rows_per_block;
@@ -496,6 +523,10 @@ __global__ __launch_bounds__(GT) void norm_act2_fwd_kernel(NormArgs2 A) {
     }
     if constexpr (sizeof(T) == 4) { if (A.amax) amax_commit(vmax, A.amax); }
 }
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act2_fwd_kernel(NormArgs2 A) { norm_act2_fwd_body<T, false>(A); }
+template <typename T>
+__global__ __launch_bounds__(GT) void norm_act2_frozen_fwd_kernel(NormArgs2 A) { norm_act2_fwd_body<T, true>(A); }
 
 template <typename T>
 __global__ __launch_bounds__(GT) void norm_act2_bwd_reduce_kernel(NormArgs2 A) {
@@ -632,6 +663,17 @@ __global__ void bn_running_update_kernel(const float *__restrict__ sums, float n
     rvar[i] = fmaf(var - rvar[i], m, rvar[i]);
 }
 
+// An eval-mode BatchNorm's statistics as the frozen passes read them: stats[c][2] = (running_mean - conv_bias, running_var).
+// conv_bias: the bias of the producing convolution that was NOT added to x -- batch statistics cancel it, running ones do not:
+// y = (x + b - rm) * rstd * gamma + beta.
+__global__ void bn_frozen_stats_kernel(const float *__restrict__ rmean, const float *__restrict__ rvar,
+                                       const float *__restrict__ bias, int c, float *__restrict__ stats) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c) return;
+    stats[2 * i] = rmean[i] - (bias ? bias[i] : 0.0f);
+    stats[2 * i + 1] = rvar[i];
+}
+
 }  // namespace
 }  // namespace epn
 
@@ -681,7 +723,7 @@ static int make_drop(double rate, const long long *state, DropArgs &D) {
 
 static int norm_act_fwd_any(const void *x_cl, int groups, long long rows, int c, const float *sums, const float *gamma,
                             const float *beta, const void *residual_cl, float eps, float slope, void *y_cl, int bf16,
-                            epn_stream_t stream, const DropArgs *drop = nullptr) {
+                            epn_stream_t stream, const DropArgs *drop = nullptr, bool frozen = false) {
     int rc = check_norm(groups, rows, c);
     if (rc) return rc;
     if (groups == 0 || rows == 0) return 0;
@@ -689,7 +731,10 @@ static int norm_act_fwd_any(const void *x_cl, int groups, long long rows, int c,
     dim3 grid;
     NormArgs A = make_norm(rows, c, eps, slope, grid, groups);
     A.x = x_cl; A.sums = sums; A.gamma = gamma; A.beta = beta; A.res = residual_cl; A.y = y_cl;
-    if (drop) {
+    if (frozen) {
+        if (bf16) EPN_LAUNCH(norm_act_frozen_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
+        else EPN_LAUNCH(norm_act_frozen_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
+    } else if (drop) {
         if (bf16) EPN_LAUNCH(norm_act_dropout_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
         else EPN_LAUNCH(norm_act_dropout_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
     } else if (bf16) EPN_LAUNCH(norm_act_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
@@ -786,7 +831,7 @@ static int pair_setup(const epn_norm_pair_side *sa, const epn_norm_pair_side *sb
 
 static int norm_act2_fwd_any(const void *xa, const void *xb, int b, long long rows, int c, const epn_norm_pair_side *sa,
                              const epn_norm_pair_side *sb, float slope, void *y, int bf16, epn_stream_t stream,
-                             float *amax = nullptr) {
+                             float *amax = nullptr, bool frozen_b = false) {
     NormArgs2 A; dim3 grid;
     int rc = pair_setup(sa, sb, b, rows, c, slope, A, grid);
     if (rc) return rc;
@@ -795,7 +840,10 @@ static int norm_act2_fwd_any(const void *xa, const void *xb, int b, long long ro
     if (b == 0 || rows == 0) return 0;
     if (!xa || !xb || !y || !sa->sums || !sb->sums) return EPN_ENULL;
     A.a.x = xa; A.b.x = xb; A.y = y; A.amax = reinterpret_cast<unsigned *>(amax);
-    if (bf16) EPN_LAUNCH(norm_act2_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
+    if (frozen_b) {
+        if (bf16) EPN_LAUNCH(norm_act2_frozen_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
+        else EPN_LAUNCH(norm_act2_frozen_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
+    } else if (bf16) EPN_LAUNCH(norm_act2_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
     else EPN_LAUNCH(norm_act2_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
     EPN_CHECK_LAUNCH();
     return 0;
@@ -917,6 +965,35 @@ extern "C" int epn_bn_running_update_f32(const float *sums, double count, const 
                        running_mean, running_var, num_batches_tracked, momentum, c);
     EPN_CHECK_LAUNCH();
     return 0;
+}
+
+// ---- frozen statistics: the forward passes of an eval-mode network (include/epn_so3conv.h "frozen statistics")
+extern "C" int epn_bn_frozen_stats_f32(const float *running_mean, const float *running_var, const float *conv_bias, int c,
+                                       float *stats_out, epn_stream_t stream) {
+    if (c < 1) return EPN_EINVAL;
+    if (!running_mean || !running_var || !stats_out) return EPN_ENULL;
+    EPN_LAUNCH(bn_frozen_stats_kernel, dim3(epn_cdiv(c, 256)), dim3(256), 0, epn_stream(stream), running_mean, running_var,
+               conv_bias, c, stats_out);
+    EPN_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int epn_norm_act_frozen_fwd_f32(const float *x_cl, long long rows, int c, const float *stats, const float *gamma,
+                                           const float *beta, const float *residual_cl, float eps, float slope, float *y_cl,
+                                           epn_stream_t stream) {
+    return norm_act_fwd_any(x_cl, 1, rows, c, stats, gamma, beta, residual_cl, eps, slope, y_cl, 0, stream, nullptr, true);
+}
+extern "C" int epn_norm_act_frozen_fwd_bf16(const void *x_cl, long long rows, int c, const float *stats, const float *gamma,
+                                            const float *beta, const void *residual_cl, float eps, float slope, void *y_cl,
+                                            epn_stream_t stream) {
+    return norm_act_fwd_any(x_cl, 1, rows, c, stats, gamma, beta, residual_cl, eps, slope, y_cl, 1, stream, nullptr, true);
+}
+extern "C" int epn_norm_act_pair_frozen_fwd(const void *xa_cl, const void *xb_cl, int b, long long rows, int c,
+                                            const epn_norm_pair_side *side_a, const epn_norm_pair_frozen_side *side_b,
+                                            float slope, void *y_cl, int bf16, epn_stream_t stream) {
+    if (!side_b) return EPN_ENULL;
+    // side b as the kernels' side: frozen statistics are one set for all clouds, instance ones one set per cloud
+    const epn_norm_pair_side sb = {side_b->stats, side_b->gamma, side_b->beta, side_b->eps, side_b->frozen ? 0 : 1};
+    return norm_act2_fwd_any(xa_cl, xb_cl, b, rows, c, side_a, &sb, slope, y_cl, bf16, stream, nullptr, side_b->frozen != 0);
 }
 
 // epilogue partials are one row per 32 tensor rows (30720 of them for the first cls layer): reduced 256 rows at a time

@@ -49,7 +49,21 @@ struct SbNorm {
     float mean[4], rstd[4], ga[4], be[4];
     float slope;
 };
+// FROZEN: A.nsums is stats[c][2] = (mean, var) of an eval-mode BatchNorm2d, read as they are (glue.hip stats4)
+template <bool FROZEN = false>
 __device__ __forceinline__ void sb_norm_load(const SbArgs &A, long long pt, int ch, SbNorm &N) {
+    if constexpr (FROZEN) {
+        const float *s = A.nsums + (size_t)ch * 2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            N.mean[i] = s[2 * i];
+            N.rstd[i] = rsqrtf(s[2 * i + 1] + A.neps);
+            N.ga[i] = A.ngamma ? A.ngamma[ch + i] : 1.0f;
+            N.be[i] = A.nbeta ? A.nbeta[ch + i] : 0.0f;
+        }
+        N.slope = A.nslope;
+        return;
+    }
     const int g = A.ngroups == 1 ? 0 : (int)(pt / A.npts_per_group);
     const float *s = A.nsums + ((size_t)g * A.c + ch) * 2;
 #pragma unroll
@@ -212,7 +226,10 @@ __device__ __forceinline__ void sb_point_dstats(const f32x4 (&acc)[4][4], const 
     }
 }
 
-template <typename T, bool SMALL>
+// (FROZEN, here and in the two kernels below: the norm on load reads frozen statistics, sb_norm_load; the trailing `true` of an
+// instance's name.  A template parameter of the kernel itself: as a device function under two kernels the body was scheduled
+// differently from the kernel it had been.)
+template <typename T, bool SMALL, bool FROZEN = false>
 __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_kernel(SbArgs A) {
     __shared__ float Ms[64 * SB_LD];
     __shared__ int bs[64], d2s[64];
@@ -270,7 +287,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_kernel(SbArgs A) {
             }
         if (A.nsums && !A.dstat_x) {
             SbNorm N;
-            sb_norm_load(A, cval ? pt : 0, choff, N);
+            sb_norm_load<FROZEN>(A, cval ? pt : 0, choff, N);
 #pragma unroll
             for (int st = 0; st < 16; ++st)
                 if (st < nst) {
@@ -321,7 +338,7 @@ typedef __bf16 sbf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned sbu32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned sbu32x4 __attribute__((ext_vector_type(4)));
 
-template <bool SMALL>
+template <bool SMALL, bool FROZEN = false>
 __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_bf16_kernel(SbArgs A) {
     __shared__ __attribute__((aligned(16))) __bf16 Mh[64 * SBH_LD];
     __shared__ __attribute__((aligned(16))) __bf16 Ml[64 * SBH_LD];
@@ -379,7 +396,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_bf16_kernel(SbArgs A)
             }
         if (A.nsums && !A.dstat_x) {
             SbNorm N;
-            sb_norm_load(A, cval ? pt : 0, choff, N);
+            sb_norm_load<FROZEN>(A, cval ? pt : 0, choff, N);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -466,7 +483,7 @@ __device__ __forceinline__ void sb_split3(const float (&x)[8], sbf16x8 &h, sbf16
     h = __builtin_bit_cast(sbf16x8, H); m = __builtin_bit_cast(sbf16x8, M); l = __builtin_bit_cast(sbf16x8, L);
 }
 
-template <bool SMALL>
+template <bool SMALL, bool FROZEN = false>
 __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void so3_basis_x3_kernel(SbArgs A) {
     __shared__ __attribute__((aligned(16))) __bf16 Mp[3][64 * SBH_LD];
     __shared__ int bs[64], d2s[64];
@@ -527,7 +544,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
             }
         if (A.nsums && !A.dstat_x) {
             SbNorm N;
-            sb_norm_load(A, cval ? pt : 0, choff, N);
+            sb_norm_load<FROZEN>(A, cval ? pt : 0, choff, N);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -752,6 +769,7 @@ struct SbNormHost {
     int groups;
     long long pts_per_group;
     float eps, slope;
+    bool frozen = false;      // sums is stats[c][2] = (mean, var), groups = 1 (epn_so3_basis_norm_frozen_*)
 };
 
 static int so3_basis_any(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
@@ -788,7 +806,19 @@ static int so3_basis_any(const void *in, const float *M, const int32_t *blocks, 
     const long long bytes = pts * na * c * (bf16 == 1 ? 2LL : 4LL);
     if (dstat_x && (!(bytes < 0x7fffff00LL && pts < (1LL << 24)) || !point_stats || !nh || out_spectral)) return EPN_EINVAL;
     const bool small_t = bytes < 0x7fffff00LL && pts < (1LL << 24) && (long long)na * c * 4 < (1LL << 24);
-    if (bf16 == 1) {
+    if (nh && nh->frozen) {
+        if (dstat_x || point_stats || amax_out || nh->groups != 1) return EPN_EINVAL;
+        if (bf16 == 1) {
+            if (small_t) EPN_LAUNCH((so3_basis_bf16_kernel<true, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
+            else EPN_LAUNCH((so3_basis_bf16_kernel<false, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
+        } else if (bf16 == 2) {
+            if (small_t) EPN_LAUNCH((so3_basis_x3_kernel<true, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
+            else EPN_LAUNCH((so3_basis_x3_kernel<false, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
+        } else {
+            if (small_t) EPN_LAUNCH((so3_basis_kernel<float, true, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
+            else EPN_LAUNCH((so3_basis_kernel<float, false, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
+        }
+    } else if (bf16 == 1) {
         if (small_t) EPN_LAUNCH(so3_basis_bf16_kernel<true>, grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
         else EPN_LAUNCH(so3_basis_bf16_kernel<false>, grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
     } else if (bf16 == 2) {                                                  // fp32, split form
@@ -902,5 +932,25 @@ extern "C" int epn_so3_basis_norm_bf16(const void *in, const float *M, const int
                                        int out_spectral, void *out, const float *sums, int groups, long long pts_per_group,
                                        const float *gamma, const float *beta, float eps, float slope, epn_stream_t stream) {
     const SbNormHost nh = {sums, gamma, beta, groups, pts_per_group, eps, slope};
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 1, stream, &nh);
+}
+
+// The same with FROZEN statistics: stats[c][2] = (mean, var) of an eval-mode BatchNorm2d (epn_bn_frozen_stats_f32), one group
+extern "C" int epn_so3_basis_norm_frozen_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
+                                             int out_spectral, float *out, const float *stats, const float *gamma,
+                                             const float *beta, float eps, float slope, epn_stream_t stream) {
+    const SbNormHost nh = {stats, gamma, beta, 1, pts, eps, slope, true};
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 0, stream, &nh);
+}
+extern "C" int epn_so3_basis_norm_frozen_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na,
+                                                   int c, int out_spectral, float *out, const float *stats, const float *gamma,
+                                                   const float *beta, float eps, float slope, epn_stream_t stream) {
+    const SbNormHost nh = {stats, gamma, beta, 1, pts, eps, slope, true};
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 2, stream, &nh);
+}
+extern "C" int epn_so3_basis_norm_frozen_bf16(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
+                                              int out_spectral, void *out, const float *stats, const float *gamma,
+                                              const float *beta, float eps, float slope, epn_stream_t stream) {
+    const SbNormHost nh = {stats, gamma, beta, 1, pts, eps, slope, true};
     return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 1, stream, &nh);
 }

@@ -49,9 +49,14 @@ class ClsOutBlockPointnet(nn.Module):
     def forward(self, x, label=None):
         f = x.feats
         for lin, norm in zip(self.linear, self.norm):
-            if self.training and ops.norm_act_supported(lin.out_channels):
+            route = S.select_glue("mlp", self.training, torch.is_grad_enabled(), 0.0, lin.out_channels, False, f.is_cuda,
+                                  ab("EPN_FUSED_EVAL"))
+            if route == "train":
                 f = ops.conv1x1(f, lin.weight, None)                       # BatchNorm cancels the bias (ops.norm_act)
                 f = ops.norm_act(f, norm, slope=0.0, conv_bias=lin.bias)   # relu(BatchNorm2d(.)) on the HIP glue
+            elif route == "eval" and ops.norm_eval_kind(norm) is not None:
+                f = ops.conv1x1(f, lin.weight, None)                       # eval(): running statistics do not cancel the bias,
+                f = ops.norm_act_eval(f, norm, slope=0.0, conv_bias=lin.bias)   # it goes into the mean the frozen pass subtracts
             else:
                 f = F.relu(norm(ops.conv1x1(f, lin.weight, lin.bias)))
         out_feat = f

@@ -138,7 +138,7 @@ def empty_cl(b, c, p, a, device, dtype=torch.float32):
 def _entry(lib, base, dtype):
     """C entry point of `base` for a feature dtype: epn_<base>_f32 | epn_<base>_bf16; the fp32 change of basis has a
     split form (bf16 matrix pipe, fp32 accuracy) that follows the GEMMs' switch (gemm.FP32_MODE)."""
-    if dtype != torch.bfloat16 and base in ("so3_basis", "so3_basis_norm", "so3_basis_stats", "so3_basis_dstats") and gemm.FP32_MODE != "native":
+    if dtype != torch.bfloat16 and base in ("so3_basis", "so3_basis_norm", "so3_basis_norm_frozen", "so3_basis_stats", "so3_basis_dstats") and gemm.FP32_MODE != "native":
         return getattr(lib, f"epn_{base}_split_f32")
     return getattr(lib, f"epn_{base}_{'bf16' if dtype == torch.bfloat16 else 'f32'}")
 
@@ -1235,7 +1235,8 @@ class _BlockGemmsFn(torch.autograd.Function):
         return (gy, None, None, None, None, None, *gws)
 
 
-def intra_so3conv_spectral(feats, W, intra_idx32, basis, pre_norm=None, pre_slope=0.01, pre_part=None, out_stats=False):
+def intra_so3conv_spectral(feats, W, intra_idx32, basis, pre_norm=None, pre_slope=0.01, pre_part=None, out_stats=False,
+                           pre_eval=False):
     """IntraSO3Conv.forward (vgtk/vgtk/so3conv/modules.py:197-200) in the block-diagonal anchor basis: same result up to
     fp32 rounding, 244 instead of 720 multiply-adds per (point, cin, cout), no [cols, 12*cin] grouped tensor; gradients
     by autograd through the same pieces (GEMMs and transforms on this library's HIP kernels)."""
@@ -1244,7 +1245,11 @@ def intra_so3conv_spectral(feats, W, intra_idx32, basis, pre_norm=None, pre_slop
     cout, kn = W.shape[0], intra_idx32.shape[1]
     _check_intra_shapes(f, W, intra_idx32)
     pts = b * p
-    if pre_norm is not None:
+    if pre_norm is not None and pre_eval:
+        # eval mode (forward only): frozen statistics read by the transform's loads, or the batch-statistics forward as below
+        # without the running-statistics update
+        y = _norm_to_spectral_eval(f, pre_norm, pre_slope, basis, pre_part)
+    elif pre_norm is not None:
         # the block's preceding norm + leaky_relu, folded into the transform's loads (training-mode statistics)
         import torch.nn as nn
         inst = isinstance(pre_norm, nn.InstanceNorm2d)
@@ -1726,6 +1731,145 @@ def norm_act(x, norm, residual=None, slope=0.01, conv_bias=None, *, dropout=0.0)
     return y
 
 
+# ---- eval mode: forward-only norm passes (frozen BatchNorm statistics, or batch statistics without the running update) ----
+def norm_eval_kind(norm):
+    """How the forward-only passes take `norm` in eval mode: "frozen" -- an nn.BatchNorm2d with running statistics, which
+    normalises with them (epn_*_frozen_*) -- or "batch" -- nn.InstanceNorm2d(affine=False, track_running_stats=False) and an
+    nn.BatchNorm2d(track_running_stats=False), whose eval arithmetic is their training arithmetic on the batch's statistics --
+    or None: not supported, the caller keeps the stock module."""
+    import torch.nn as nn
+    if isinstance(norm, nn.BatchNorm2d):
+        if not norm.track_running_stats or norm.running_mean is None:
+            return "batch"
+        rm, rv = norm.running_mean, norm.running_var
+        return "frozen" if rm.dtype == torch.float32 and rv.dtype == torch.float32 else None
+    if isinstance(norm, nn.InstanceNorm2d) and not norm.affine and not norm.track_running_stats:
+        return "batch"
+    return None
+
+
+def _eval_kind(norm):
+    kind = norm_eval_kind(norm)
+    if kind is None:
+        raise TypeError(f"no eval-mode HIP form for {norm!r}")
+    return kind
+
+
+def _forward_only(what, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{what} is forward only: call it under torch.no_grad(), or with inputs and parameters that do not "
+                           "require grad")
+
+
+def _frozen_stats(norm, conv_bias):
+    """stats[c][2] = (running_mean - conv_bias, running_var) of an eval-mode BatchNorm2d, written on the device from the module's
+    buffers on EVERY call (a few KB; weights may be reloaded, and a captured graph follows them): nothing is cached."""
+    rm, rv = norm.running_mean, norm.running_var
+    c = rm.numel()
+    stats = torch.empty((c, 2), dtype=torch.float32, device=rm.device)
+    bias = conv_bias.detach().float().contiguous() if conv_bias is not None else None
+    _lib.check(_lib.get_lib().epn_bn_frozen_stats_f32(_lib.dev_ptr(rm.contiguous(), "running_mean"),
+                                                      _lib.dev_ptr(rv.contiguous(), "running_var"),
+                                                      _lib.dev_ptr(bias, "conv_bias"), c, _lib.dev_ptr(stats, "stats"),
+                                                      _lib.stream_of(stats)), "bn_frozen_stats")
+    return stats
+
+
+def _affine(norm):
+    g, bt = getattr(norm, "weight", None), getattr(norm, "bias", None)
+    return (g.detach().contiguous() if g is not None else None), (bt.detach().contiguous() if bt is not None else None)
+
+
+def norm_act_eval(x, norm, residual=None, slope=0.01, conv_bias=None):
+    """leaky_relu(norm(x)) (+ residual) as `norm` computes it in eval() mode; forward only (raises when an input requires grad
+    while grad is enabled).  nn.BatchNorm2d with running statistics: ONE streaming pass on the frozen statistics
+    (epn_norm_act_frozen_fwd_*), the module's buffers are read and never written.  Norms without running statistics
+    (norm_eval_kind "batch"): the training forward on the batch's statistics, with no running-statistics update.
+    conv_bias: bias of the convolution that produced x, NOT added to x: frozen statistics do not cancel it, so it goes into the
+    mean the pass subtracts, y = (x + b - running_mean) * rstd * gamma + beta; batch statistics cancel it (norm_act).
+    The output carries no max|y| tag (two-piece fp16 GEMMs scan it)."""
+    kind = _eval_kind(norm)
+    _forward_only("norm_act_eval", x, residual, conv_bias, *norm.parameters())
+    if kind == "batch":
+        import torch.nn as nn
+        with torch.no_grad():
+            return NormActFn.apply(x, getattr(norm, "weight", None), getattr(norm, "bias", None), residual, conv_bias,
+                                   isinstance(norm, nn.InstanceNorm2d), norm.eps, slope)[0]
+    lib = _lib.get_lib()
+    xc = to_cl(x, "x")
+    b, c, p, a = xc.shape
+    dt = xc.dtype
+    stats = _frozen_stats(norm, conv_bias)
+    g, bt = _affine(norm)
+    y = empty_cl(b, c, p, a, xc.device, dt)
+    r = cast_feats(to_cl(residual, "residual"), dt) if residual is not None else None
+    _lib.check(_entry(lib, "norm_act_frozen_fwd", dt)(_cl_ptr(xc), b * p * a, c, _lib.dev_ptr(stats, "stats"),
+                                                      _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"),
+                                                      _cl_ptr(r) if r is not None else ctypes.c_void_p(0), float(norm.eps),
+                                                      float(slope), _cl_ptr(y), _lib.stream_of(xc)), "norm_act_frozen_fwd")
+    return y
+
+
+def norm_act_pair_eval(xa, norm_a, xb, norm_b, conv_bias_b=None, slope=0.01, part_b=None, part_a=None):
+    """leaky_relu(norm_a(xa)) + leaky_relu(norm_b(xb)) in one pass in eval() mode, forward only.  norm_a: a norm without running
+    statistics (a separable block's InstanceNorm2d: statistics of xa, from part_a when given).  norm_b: an nn.BatchNorm2d with
+    running statistics -- frozen side, epn_norm_act_pair_frozen_fwd; conv_bias_b goes into its mean as in norm_act_eval -- or a
+    norm without them: the training forward of norm_act_pair (statistics from part_b when given), no running update."""
+    import torch.nn as nn
+    ka, kb = _eval_kind(norm_a), _eval_kind(norm_b)
+    if ka != "batch":
+        raise TypeError("norm_act_pair_eval: side a takes a norm without running statistics")
+    _forward_only("norm_act_pair_eval", xa, xb, conv_bias_b, *norm_a.parameters(), *norm_b.parameters())
+    ia = isinstance(norm_a, nn.InstanceNorm2d)
+    if kb == "batch":
+        with torch.no_grad():
+            return NormActPairFn.apply(xa, xb, getattr(norm_a, "weight", None), getattr(norm_a, "bias", None),
+                                       getattr(norm_b, "weight", None), getattr(norm_b, "bias", None), conv_bias_b, ia,
+                                       isinstance(norm_b, nn.InstanceNorm2d), norm_a.eps, norm_b.eps, slope, part_b, part_a)[0]
+    lib = _lib.get_lib()
+    xac = to_cl(xa, "xa")
+    xbc = cast_feats(to_cl(xb, "xb"), xac.dtype)
+    b, c, p, a = xac.shape
+    rows = p * a
+    sums_a = _stats(xac, b if ia else 1, rows if ia else b * rows, c, part_a, a)
+    ga, ba = _affine(norm_a)
+    gb, bb = _affine(norm_b)
+    sa = _pair_side(sums_a, ga, ba, norm_a.eps, ia)
+    stats_b = _frozen_stats(norm_b, conv_bias_b)
+    sb = _lib.NormPairFrozenSide()
+    sb.stats, sb.gamma, sb.beta = _lib.dev_ptr(stats_b, "stats"), _lib.dev_ptr(gb, "gamma"), _lib.dev_ptr(bb, "beta")
+    sb.eps, sb.frozen = float(norm_b.eps), 1
+    y = empty_cl(b, c, p, a, xac.device, xac.dtype)
+    _lib.check(lib.epn_norm_act_pair_frozen_fwd(_cl_ptr(xac), _cl_ptr(xbc), b, rows, c, ctypes.byref(sa), ctypes.byref(sb),
+                                                float(slope), _cl_ptr(y), int(xac.dtype == torch.bfloat16),
+                                                _lib.stream_of(xac)), "norm_act_pair_frozen_fwd")
+    return y
+
+
+def _norm_to_spectral_eval(f, norm, slope, basis, part=None):
+    """ToSpectral(leaky_relu(norm(f))) in eval() mode (forward only), the norm applied as the basis change loads its rows: frozen
+    statistics (epn_so3_basis_norm_frozen_*), or NormToSpectralFn's forward on the batch's statistics without the running
+    update.  f: channels-last [b,c,p,a]."""
+    import torch.nn as nn
+    kind = _eval_kind(norm)
+    _forward_only("intra_so3conv(pre_eval=True)", f, *norm.parameters())
+    if kind == "batch":
+        with torch.no_grad():
+            return NormToSpectralFn.apply(f, getattr(norm, "weight", None), getattr(norm, "bias", None), None,
+                                          isinstance(norm, nn.InstanceNorm2d), norm.eps, slope, basis, part)[0]
+    lib = _lib.get_lib()
+    b, c, p, na = f.shape
+    stats = _frozen_stats(norm, None)
+    g, bt = _affine(norm)
+    y = torch.empty(na * b * p * c, dtype=f.dtype, device=f.device)
+    _run(("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, f.device), "so3_basis_norm_frozen",
+         _entry(lib, "so3_basis_norm_frozen", f.dtype), _cl_ptr(f), _lib.dev_ptr(basis.Ut, "M"),
+         _lib.dev_ptr(basis.blocks, "blocks", torch.int32), ctypes.c_longlong(b * p), na, c, 1, ctypes.c_void_p(y.data_ptr()),
+         _lib.dev_ptr(stats, "stats"), _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), float(norm.eps), float(slope),
+         _lib.stream_of(f))
+    return y
+
+
 def deterministic_bwd(dtype):
     """Atomic-free, bitwise repeatable InterSO3Conv data gradient?  EPN_DETERMINISTIC = 1 | 0 (default 0).  Measured on
     MI355X: the per-slot slab + ordered reduction costs 12 % of a bf16 step (rotation network, 673 vs 767 clouds/s) and
@@ -1842,9 +1986,10 @@ def intra_takes_spectral(cin, cout, intra_idx32, is_cuda=True):
                         lambda: spectral_basis(intra_idx32) is not None) == "spectral"
 
 
-def intra_so3conv(feats, W, intra_idx32, pre_norm=None, pre_part=None, out_stats=False):
+def intra_so3conv(feats, W, intra_idx32, pre_norm=None, pre_part=None, out_stats=False, pre_eval=False):
     """pre_norm: an nn.BatchNorm2d / nn.InstanceNorm2d(affine=False) whose leaky_relu(norm(feats)) is the actual input
-    (training mode); only with intra_takes_spectral(...) -- other forms get the normalised tensor from ops.norm_act.
+    (training mode; pre_eval=True: eval mode, forward only, see norm_act_eval); only with intra_takes_spectral(...) -- other
+    forms get the normalised tensor from ops.norm_act / norm_act_eval.
     pre_part: block partials of feats' per-channel statistics from its producer's epilogue (spectral form only).
     out_stats: return (out, part) -- part = per-point partials of out's statistics (spectral form) or None."""
     bf = feats.dtype == torch.bfloat16
@@ -1852,9 +1997,9 @@ def intra_so3conv(feats, W, intra_idx32, pre_norm=None, pre_part=None, out_stats
                         lambda: spectral_basis(intra_idx32) is not None, bf)
     if form == "spectral":
         return intra_so3conv_spectral(feats, W, intra_idx32, spectral_basis(intra_idx32), pre_norm=pre_norm,
-                                      pre_part=pre_part, out_stats=out_stats)
+                                      pre_part=pre_part, out_stats=out_stats, pre_eval=pre_eval)
     if pre_norm is not None:
-        feats = norm_act(feats, pre_norm)
+        feats = norm_act_eval(feats, pre_norm) if pre_eval else norm_act(feats, pre_norm)
     if form == "split":
         out = IntraSO3ConvSplitFn.apply(feats, W, intra_idx32)
     elif bf:                                   # odd widths: fp32 kernels between two casts

@@ -99,6 +99,37 @@ def _hip_dropout_rate(dropout):
     return dropout.p if 0.0 < dropout.p < 1.0 and ab("EPN_FUSED_DROPOUT") == "1" else None
 
 
+def select_glue(block, training, grad_enabled, hip_dropout_rate, c_out, use_intra, is_cuda, switch):
+    """Where does a block's glue (norm + leaky_relu (+ dropout), skip branch) run?  -> "train": the HIP glue on batch statistics
+    (ops.norm_act ...) | "eval": the forward-only HIP glue of eval() mode (ops.norm_act_eval ...: frozen BatchNorm statistics,
+    dropout the identity) | "stock": the torch modules.
+    block: "separable" (FusedSeparableBlock) | "inter" (InterBlock) | "mlp" (models.ClsOutBlockPointnet's 1x1 conv + BatchNorm2d
+    + relu); hip_dropout_rate: _hip_dropout_rate(block.dropout); use_intra: the separable block's; is_cuda: the features';
+    switch: ab("EPN_FUSED_EVAL").
+    Training mode: each block's own conditions, as they were before there was an eval route -- the separable block never asked
+    for the device (a CPU tensor raises in ops.to_cl), the mlp never had dropout.  Eval mode: "eval" when grad is disabled, the
+    tensors are on the GPU, the width is one the norm kernels take and the switch is on -- whatever the dropout rate, since no
+    mask is drawn; a separable block without its intra convolution has no HIP glue in either mode.  Eval with grad ENABLED
+    (fine-tuning with frozen BatchNorm) stays on the stock modules: the frozen passes have no backward.  The caller still
+    checks ops.norm_eval_kind of its norms."""
+    supported = ops.norm_act_supported(c_out)
+    if training:
+        if block == "separable":
+            ok = hip_dropout_rate is not None and supported and use_intra
+        elif block == "inter":
+            ok = hip_dropout_rate is not None and is_cuda and supported
+        else:
+            ok = supported
+        return "train" if ok else "stock"
+    if grad_enabled or not is_cuda or not supported or switch != "1" or (block == "separable" and not use_intra):
+        return "stock"
+    return "eval"
+
+
+def _eval_norms_ok(*norms):
+    return all(ops.norm_eval_kind(n) is not None for n in norms)
+
+
 class SeparableBlock(nn.Module):
     """One SeparableSO3ConvBlock (SPConvNets/utils/base_so3conv.py:168-212) with the reference's module tree, so a
     reference checkpoint's keys (`inter_conv.conv.basic_conv.W`, `inter_conv.norm.*`, `intra_conv.conv.*`,
@@ -147,16 +178,28 @@ class FusedSeparableBlock(SeparableBlock):
     """Same module tree / state_dict as SeparableBlock, with the glue on the HIP "block glue" kernels:
     norm + leaky_relu (+ the residual add) are two streaming passes each, the 1x1 skip convolution runs on the intra
     GEMM kernel (one anchor "neighbour", identity index) -- everything stays channels-last, no layout copies.
-    Training-mode semantics (batch statistics); eval mode falls back to the stock modules.  With dropout_rate in (0, 1) the
+    Training mode: batch statistics.  With dropout_rate in (0, 1) the
     block stays here: both main-branch norms draw their mask inside their own passes (ops.norm_act(..., dropout=rate), the
     skip branch is added unmasked as in base_so3conv.py:205-211) in the plain forms -- the norm-on-load and pair forms do not
-    take dropout yet; a rate of 1 takes the stock modules."""
+    take dropout yet; a rate of 1 takes the stock modules.
+    eval() under torch.no_grad(): the same schedule on the forward-only passes (select_glue "eval"; ops.norm_act_eval,
+    norm_act_pair_eval, the pre_eval route of the intra convolution): a BatchNorm2d normalises with its running statistics
+    (frozen form, nothing is reduced or updated), an InstanceNorm2d computes as in training with its statistics from the
+    producers' epilogues, dropout is the identity and its generator is not touched.  eval() with grad enabled, and
+    EPN_FUSED_EVAL=0, take the stock modules."""
 
     def forward(self, x, inter_idx=None, inter_w=None):
         c_out = self.inter_conv.conv.dim_out
         drop = _hip_dropout_rate(self.dropout)
-        if (not self.training) or drop is None or not ops.norm_act_supported(c_out) or not self.use_intra:
+        route = select_glue("separable", self.training, torch.is_grad_enabled(), drop, c_out, self.use_intra, x.feats.is_cuda,
+                            ab("EPN_FUSED_EVAL"))
+        if route == "eval" and not _eval_norms_ok(self.inter_conv.norm, self.intra_conv.norm, self.norm):
+            route = "stock"
+        if route == "stock":
             return super().forward(x, inter_idx, inter_w)
+        ev = route == "eval"
+        if ev:
+            drop = 0.0                             # nn.Dropout in eval mode: the identity, whatever its rate
         import os
         conv = self.inter_conv.conv
         # x.feats feeds the inter convolution AND the skip branch: the convolution hands back the tensor for the second use
@@ -182,14 +225,22 @@ class FusedSeparableBlock(SeparableBlock):
 
         pair = ab("EPN_NORM_PAIR") == "1" and not drop    # skip norm folded into the block's final pass
 
+        # eval mode, BatchNorm2d on the skip branch: frozen statistics, nothing to take from the GEMM's epilogue
+        frozen_skip = ev and ops.norm_eval_kind(self.norm) == "frozen"
+
         def skip_branch():
             sk = skip
             if self.stride > 1:                                    # batched_index_select(skip, 2, sample_idx) on rows
                 sk = ops.gather_rows(sk, sample_idx)
-            if pair and epi:
+            if pair and epi and not frozen_skip:
                 return ops.conv1x1(sk, self.skip_conv.weight, None, col_stats=True, x_amax=x_amax)   # (tensor, partial statistics)
-            sk = ops.conv1x1(sk, self.skip_conv.weight, None, x_amax=x_amax)    # the norm cancels the bias: see ops.norm_act
-            return (sk, None) if pair else (ops.norm_act(sk, self.norm, conv_bias=self.skip_conv.bias), None)
+            # the bias is not added: batch statistics cancel it (ops.norm_act), frozen ones take it into their mean (ops.norm_act_eval)
+            sk = ops.conv1x1(sk, self.skip_conv.weight, None, x_amax=x_amax)
+            if pair:
+                return sk, None
+            if ev:
+                return ops.norm_act_eval(sk, self.norm, conv_bias=self.skip_conv.bias), None
+            return ops.norm_act(sk, self.norm, conv_bias=self.skip_conv.bias), None
 
         side = None
         if os.environ.get("EPN_SKIP_STREAM", "1") == "1" and skip.is_cuda:
@@ -206,12 +257,13 @@ class FusedSeparableBlock(SeparableBlock):
             iconv = self.intra_conv.conv
             iconv.want_out_stats = epi and pair
             try:
-                z = iconv(zptk.SphericalPointCloud(y.xyz, y.feats, y.anchors), pre_norm=self.inter_conv.norm, pre_part=y_part)
+                z = iconv(zptk.SphericalPointCloud(y.xyz, y.feats, y.anchors), pre_norm=self.inter_conv.norm, pre_part=y_part,
+                          pre_eval=ev)
             finally:
                 iconv.want_out_stats = False
             z_part = iconv.__dict__.pop("_out_stats", None)
         else:
-            feat = ops.norm_act(y.feats, self.inter_conv.norm, dropout=drop)
+            feat = ops.norm_act_eval(y.feats, self.inter_conv.norm) if ev else ops.norm_act(y.feats, self.inter_conv.norm, dropout=drop)
             z = self.intra_conv.conv(zptk.SphericalPointCloud(y.xyz, feat, y.anchors))
             z_part = None
         if side is None:
@@ -224,8 +276,11 @@ class FusedSeparableBlock(SeparableBlock):
         if pair:
             # leaky(IN(z)) + leaky(norm(skip conv)) in ONE pass: the skip branch's normalised tensor is never written, the
             # backward reads the output gradient once per pass for both norms
-            out = ops.norm_act_pair(z.feats, self.intra_conv.norm, s, self.norm, conv_bias_b=self.skip_conv.bias,
-                                    part_b=s_part, part_a=z_part)
+            pair_fn = ops.norm_act_pair_eval if ev else ops.norm_act_pair
+            out = pair_fn(z.feats, self.intra_conv.norm, s, self.norm, conv_bias_b=self.skip_conv.bias,
+                          part_b=s_part, part_a=z_part)
+        elif ev:
+            out = ops.norm_act_eval(z.feats, self.intra_conv.norm, residual=s)
         else:
             # leaky(IN(z)) (masked when the block has dropout) + skip in the same pass
             out = ops.norm_act(z.feats, self.intra_conv.norm, residual=s, dropout=drop)
@@ -248,8 +303,12 @@ class InterBlock(nn.Module):
     def forward(self, x, inter_idx=None, inter_w=None):
         inter_idx, inter_w, sample_idx, y = self.conv(x, inter_idx, inter_w)
         drop = _hip_dropout_rate(self.dropout)
-        if self.training and drop is not None and y.feats.is_cuda and ops.norm_act_supported(y.feats.shape[1]):
+        route = select_glue("inter", self.training, torch.is_grad_enabled(), drop, y.feats.shape[1], False, y.feats.is_cuda,
+                            ab("EPN_FUSED_EVAL"))
+        if route == "train":
             feat = ops.norm_act(y.feats, self.norm, dropout=drop)
+        elif route == "eval" and _eval_norms_ok(self.norm):
+            feat = ops.norm_act_eval(y.feats, self.norm)     # nn.Dropout in eval mode: the identity
         else:
             feat = F.leaky_relu(self.norm(y.feats))
             if self.training and self.dropout is not None:

@@ -161,15 +161,17 @@ class IntraSO3Conv(nn.Module):
             self._idx32_cache, self._idx32_key = src.int().contiguous(), key
         return self._idx32_cache
 
-    def forward(self, x, pre_norm=None, pre_part=None):
+    def forward(self, x, pre_norm=None, pre_part=None, pre_eval=False):
         """pre_norm (extension, used by schedule.FusedSeparableBlock): the norm module whose leaky_relu(norm(x.feats)) is the
         input -- folded into the convolution's basis change when it takes the block-diagonal form; pre_part: partial
-        per-channel statistics of x.feats from the epilogue of the GEMM that produced it."""
+        per-channel statistics of x.feats from the epilogue of the GEMM that produced it; pre_eval: the norm as it computes in
+        eval() mode (forward only, ops.norm_act_eval)."""
         if getattr(self, "want_out_stats", False):       # set by a block whose norm follows: see ops.intra_so3conv
             feats, self._out_stats = ops.intra_so3conv(x.feats, self.basic_conv.W, self._idx32(), pre_norm=pre_norm,
-                                                       pre_part=pre_part, out_stats=True)
+                                                       pre_part=pre_part, out_stats=True, pre_eval=pre_eval)
         else:
-            feats = ops.intra_so3conv(x.feats, self.basic_conv.W, self._idx32(), pre_norm=pre_norm, pre_part=pre_part)
+            feats = ops.intra_so3conv(x.feats, self.basic_conv.W, self._idx32(), pre_norm=pre_norm, pre_part=pre_part,
+                                      pre_eval=pre_eval)
         return SphericalPointCloud(x.xyz, feats, self.anchors)
 
     def takes_spectral_form(self, is_cuda=True):

@@ -309,6 +309,42 @@ int epn_norm_act_dropout_bwd_apply_bf16(const void *x_cl, const void *dy_cl, int
 int epn_dropout_mask_u8(unsigned char *mask, long long numel, double rate, const long long *state, epn_stream_t stream);
 int epn_dropout_state_next(long long *state, long long *saved, epn_stream_t stream);
 
+/* Frozen statistics: the forward passes above for a network in eval() mode, where torch.nn.BatchNorm2d normalises with its
+ * running statistics instead of the batch's (forward only: no backward forms, no running-statistics update, no maximum
+ * variants -- a consumer that needs max |y| scans the tensor).  Every pass reads stats f32[c][2] = (mean, var) AS THEY ARE,
+ * rstd = rsqrt(var + eps), one group: the statistics are never turned into (sum x, sum x^2) for the entry points above,
+ * because var = s2 / rows - mean^2 cancels when mean^2 >> var.  Sizes as their twins: c % 4 == 0, 256 % (c / 4) == 0.
+ *
+ * epn_bn_frozen_stats_f32 writes stats_out[c][2] = (running_mean - conv_bias, running_var) in one launch, reading through the
+ * pointers (no host synchronisation: an eval forward can be captured in a graph, and a replay follows statistics changed in
+ * place).  conv_bias (or NULL): the bias of the producing convolution when it was NOT added to x.  Batch statistics cancel such
+ * a bias, running statistics do not: y = (x + b - running_mean) * rstd * gamma + beta.  Replaces torch.nn.BatchNorm2d in eval
+ * mode inside SeparableSO3ConvBlock / InterSO3ConvBlock / ClsOutBlockPointnet (base_so3conv.py:168-212 / :87-126 / :358-448). */
+int epn_bn_frozen_stats_f32(const float *running_mean, const float *running_var, const float *conv_bias, int c,
+                            float *stats_out, epn_stream_t stream);
+/* y = leaky((x - mean) * rsqrt(var + eps) * gamma + beta, slope) (+ residual); x_cl [rows][c], rows = b*p*a; gamma / beta /
+ * residual optional.  The twin of epn_norm_act_fwd_*; replaces relu(torch.nn.BatchNorm2d(x)) in eval mode
+ * (base_so3conv.py:168-212 / :87-126, and with slope = 0 the head's mlp, :358-448). */
+int epn_norm_act_frozen_fwd_f32(const float *x_cl, long long rows, int c, const float *stats, const float *gamma,
+                                const float *beta, const float *residual_cl, float eps, float slope, float *y_cl,
+                                epn_stream_t stream);
+int epn_norm_act_frozen_fwd_bf16(const void *x_cl, long long rows, int c, const float *stats, const float *gamma,
+                                 const float *beta, const void *residual_cl, float eps, float slope, void *y_cl,
+                                 epn_stream_t stream);
+/* The twin of epn_norm_act_pair_fwd: y = leaky_relu(norm_a(xa)) + leaky_relu(norm_b(xb)) with side a as there (statistics
+ * from its sums) and side b either frozen (stats[c][2] = (mean, var): torch.nn.BatchNorm2d in eval mode on the skip branch,
+ * base_so3conv.py:168-212) or instance (stats = sums[b][c][2] per cloud, as an "instance" epn_norm_pair_side). */
+typedef struct epn_norm_pair_frozen_side {
+    const float *stats;     /* frozen: [c][2] = (mean, var);  else [b][c][2] = (sum x, sum x^2) per cloud */
+    const float *gamma;     /* [c] or NULL */
+    const float *beta;      /* [c] or NULL */
+    float eps;
+    int frozen;             /* 1: frozen statistics, 0: instance statistics from sums */
+} epn_norm_pair_frozen_side;
+int epn_norm_act_pair_frozen_fwd(const void *xa_cl, const void *xb_cl, int b, long long rows, int c,
+                                 const epn_norm_pair_side *side_a, const epn_norm_pair_frozen_side *side_b, float slope,
+                                 void *y_cl, int bf16, epn_stream_t stream);
+
 /* replaces vgtk.cuda.grouping.initial_anchor_query (vgtk/vgtk/cuda/grouping_cuda.cpp:138-158, kernel
  * grouping_cuda_kernel.cu:116-167; only consumer: KernelPropagation, vgtk/vgtk/so3conv/modules.py:57-119).
  *   centers f32[b][3][nc]   xyz f32[m][3] (fragment points, shared by the batch)   kernel_points f32[ks][na][3]
@@ -749,6 +785,18 @@ int epn_so3_basis_split_f32(const float *in, const float *M, const int32_t *bloc
 int epn_so3_basis_norm_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                  int out_spectral, float *out, const float *sums, int groups, long long pts_per_group,
                                  const float *gamma, const float *beta, float eps, float slope, epn_stream_t stream);
+/* The twins of epn_so3_basis_norm_* with frozen statistics (see "Frozen statistics" above): stats[c][2] = (mean, var) from
+ * epn_bn_frozen_stats_f32, one group.  Replace torch.nn.BatchNorm2d in eval mode + leaky_relu in front of IntraSO3Conv
+ * (base_so3conv.py:168-212 / :87-126). */
+int epn_so3_basis_norm_frozen_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
+                                  int out_spectral, float *out, const float *stats, const float *gamma, const float *beta,
+                                  float eps, float slope, epn_stream_t stream);
+int epn_so3_basis_norm_frozen_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
+                                        int out_spectral, float *out, const float *stats, const float *gamma,
+                                        const float *beta, float eps, float slope, epn_stream_t stream);
+int epn_so3_basis_norm_frozen_bf16(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
+                                   int out_spectral, void *out, const float *stats, const float *gamma, const float *beta,
+                                   float eps, float slope, epn_stream_t stream);
 /* The backward reduction of the block's FIRST norm (InterSO3ConvBlock's norm + leaky_relu in front of IntraSO3Conv,
  * SPConvNets/utils/base_so3conv.py:196-204) taken from the kernel that produces its output gradient: the inverse basis change
  * of the spectral gradient writes dy (plain layout) AND, from its accumulators, per point the partial sums
