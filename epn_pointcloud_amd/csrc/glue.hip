@@ -679,6 +679,13 @@ __global__ void bn_frozen_stats_kernel(const float *__restrict__ rmean, const fl
 
 using namespace epn;
 
+// one launch of a kernel template on the feature dtype of the call: kern<__bf16> or kern<float>
+#define EPN_LAUNCH_DT(bf16, kern, ...)                   \
+    do {                                                 \
+        if (bf16) EPN_LAUNCH(kern<__bf16>, __VA_ARGS__); \
+        else EPN_LAUNCH(kern<float>, __VA_ARGS__);       \
+    } while (0)
+
 extern "C" size_t epn_norm_workspace_bytes(int groups, long long rows, int c) {
     if (check_norm(groups, rows, c) || groups == 0 || rows == 0) return 0;
     dim3 grid;
@@ -701,8 +708,7 @@ static int chan_stats_any(const void *x_cl, int groups, long long rows, int c, f
     dim3 grid;
     NormArgs A = make_norm(rows, c, 0.f, 0.f, grid, groups);
     A.x = x_cl; A.out_sums = static_cast<float *>(workspace);
-    if (bf16) EPN_LAUNCH(chan_stats_kernel<__bf16>, grid, dim3(GT), 0, st, A);
-    else EPN_LAUNCH(chan_stats_kernel<float>, grid, dim3(GT), 0, st, A);
+    EPN_LAUNCH_DT(bf16, chan_stats_kernel, grid, dim3(GT), 0, st, A);
     EPN_CHECK_LAUNCH();
     EPN_LAUNCH_AUX(stats_finish_kernel, dim3(epn_cdiv(2 * c, 16), groups), dim3(256), 0, st, A.out_sums, (int)grid.x,
                        c * 2, sums);
@@ -731,14 +737,24 @@ static int norm_act_fwd_any(const void *x_cl, int groups, long long rows, int c,
     dim3 grid;
     NormArgs A = make_norm(rows, c, eps, slope, grid, groups);
     A.x = x_cl; A.sums = sums; A.gamma = gamma; A.beta = beta; A.res = residual_cl; A.y = y_cl;
-    if (frozen) {
-        if (bf16) EPN_LAUNCH(norm_act_frozen_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
-        else EPN_LAUNCH(norm_act_frozen_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
-    } else if (drop) {
-        if (bf16) EPN_LAUNCH(norm_act_dropout_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
-        else EPN_LAUNCH(norm_act_dropout_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
-    } else if (bf16) EPN_LAUNCH(norm_act_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
-    else EPN_LAUNCH(norm_act_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
+    if (frozen) EPN_LAUNCH_DT(bf16, norm_act_frozen_fwd_kernel, grid, dim3(GT), 0, epn_stream(stream), A);
+    else if (drop) EPN_LAUNCH_DT(bf16, norm_act_dropout_fwd_kernel, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
+    else EPN_LAUNCH_DT(bf16, norm_act_fwd_kernel, grid, dim3(GT), 0, epn_stream(stream), A);
+    EPN_CHECK_LAUNCH();
+    return 0;
+}
+
+// last step of a norm's backward reduction: block partials part[g][block][c][2] -> dsums, dgamma, dbeta.  aux: how the
+// launch is noted (EPN_LAUNCH_AUX after a streaming pass of the same call, EPN_LAUNCH as an entry point's own kernel)
+static int bwd_finish(const float *partials, int groups, int blocks_per_group, int c, const float *gamma, float *dsums,
+                      float *dgamma, float *dbeta, bool aux, hipStream_t st) {
+    if (groups > 1) {                        // several groups accumulate with atomics; one group stores
+        if (dgamma) EPN_HIP(hipMemsetAsync(dgamma, 0, sizeof(float) * c, st));
+        if (dbeta) EPN_HIP(hipMemsetAsync(dbeta, 0, sizeof(float) * c, st));
+    }
+    ::epn::note_kernel(reinterpret_cast<const void *>(&bwd_finish_kernel), aux);
+    hipLaunchKernelGGL(bwd_finish_kernel, dim3(epn_cdiv(c, 16), groups), dim3(256), 0, st, partials, blocks_per_group, c, gamma,
+                       dsums, dgamma, dbeta);
     EPN_CHECK_LAUNCH();
     return 0;
 }
@@ -763,20 +779,10 @@ static int norm_act_bwd_reduce_any(const void *x_cl, const void *dy_cl, int grou
     NormArgs A = make_norm(rows, c, eps, slope, grid, groups);
     A.x = x_cl; A.dy = dy_cl; A.sums = sums; A.gamma = gamma; A.beta = beta;
     A.out_sums = static_cast<float *>(workspace);
-    if (drop) {
-        if (bf16) EPN_LAUNCH(norm_act_dropout_bwd_reduce_kernel<__bf16>, grid, dim3(GT), 0, st, A, *drop);
-        else EPN_LAUNCH(norm_act_dropout_bwd_reduce_kernel<float>, grid, dim3(GT), 0, st, A, *drop);
-    } else if (bf16) EPN_LAUNCH(norm_act_bwd_reduce_kernel<__bf16>, grid, dim3(GT), 0, st, A);
-    else EPN_LAUNCH(norm_act_bwd_reduce_kernel<float>, grid, dim3(GT), 0, st, A);
+    if (drop) EPN_LAUNCH_DT(bf16, norm_act_dropout_bwd_reduce_kernel, grid, dim3(GT), 0, st, A, *drop);
+    else EPN_LAUNCH_DT(bf16, norm_act_bwd_reduce_kernel, grid, dim3(GT), 0, st, A);
     EPN_CHECK_LAUNCH();
-    if (groups > 1) {                        // several groups accumulate with atomics; one group stores
-        if (dgamma) EPN_HIP(hipMemsetAsync(dgamma, 0, sizeof(float) * c, st));
-        if (dbeta) EPN_HIP(hipMemsetAsync(dbeta, 0, sizeof(float) * c, st));
-    }
-    EPN_LAUNCH_AUX(bwd_finish_kernel, dim3(epn_cdiv(c, 16), groups), dim3(256), 0, st, A.out_sums, (int)grid.x, c, gamma,
-                       dsums, dgamma, dbeta);
-    EPN_CHECK_LAUNCH();
-    return 0;
+    return bwd_finish(A.out_sums, groups, (int)grid.x, c, gamma, dsums, dgamma, dbeta, true, st);
 }
 
 static int amax_prepare(float *amax, int bf16, hipStream_t st) {
@@ -800,11 +806,8 @@ static int norm_act_bwd_apply_any(const void *x_cl, const void *dy_cl, int group
     NormArgs A = make_norm(rows, c, eps, slope, grid, groups);
     A.x = x_cl; A.dy = dy_cl; A.sums = sums; A.dsums = dsums; A.gamma = gamma; A.beta = beta; A.y = dx_cl;
     A.amax = reinterpret_cast<unsigned *>(amax);
-    if (drop) {
-        if (bf16) EPN_LAUNCH(norm_act_dropout_bwd_apply_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
-        else EPN_LAUNCH(norm_act_dropout_bwd_apply_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
-    } else if (bf16) EPN_LAUNCH(norm_act_bwd_apply_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
-    else EPN_LAUNCH(norm_act_bwd_apply_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
+    if (drop) EPN_LAUNCH_DT(bf16, norm_act_dropout_bwd_apply_kernel, grid, dim3(GT), 0, epn_stream(stream), A, *drop);
+    else EPN_LAUNCH_DT(bf16, norm_act_bwd_apply_kernel, grid, dim3(GT), 0, epn_stream(stream), A);
     EPN_CHECK_LAUNCH();
     return 0;
 }
@@ -840,11 +843,8 @@ static int norm_act2_fwd_any(const void *xa, const void *xb, int b, long long ro
     if (b == 0 || rows == 0) return 0;
     if (!xa || !xb || !y || !sa->sums || !sb->sums) return EPN_ENULL;
     A.a.x = xa; A.b.x = xb; A.y = y; A.amax = reinterpret_cast<unsigned *>(amax);
-    if (frozen_b) {
-        if (bf16) EPN_LAUNCH(norm_act2_frozen_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
-        else EPN_LAUNCH(norm_act2_frozen_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
-    } else if (bf16) EPN_LAUNCH(norm_act2_fwd_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
-    else EPN_LAUNCH(norm_act2_fwd_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
+    if (frozen_b) EPN_LAUNCH_DT(bf16, norm_act2_frozen_fwd_kernel, grid, dim3(GT), 0, epn_stream(stream), A);
+    else EPN_LAUNCH_DT(bf16, norm_act2_fwd_kernel, grid, dim3(GT), 0, epn_stream(stream), A);
     EPN_CHECK_LAUNCH();
     return 0;
 }
@@ -874,8 +874,7 @@ static int norm_act2_bwd_reduce_any(const void *xa, const void *xb, const void *
     A.a.x = xa; A.b.x = xb; A.dy = dy;
     A.a.part = static_cast<float *>(workspace);
     A.b.part = A.a.part + (size_t)b * grid.x * c * 2;
-    if (bf16) EPN_LAUNCH(norm_act2_bwd_reduce_kernel<__bf16>, grid, dim3(GT), 0, st, A);
-    else EPN_LAUNCH(norm_act2_bwd_reduce_kernel<float>, grid, dim3(GT), 0, st, A);
+    EPN_LAUNCH_DT(bf16, norm_act2_bwd_reduce_kernel, grid, dim3(GT), 0, st, A);
     EPN_CHECK_LAUNCH();
     // finishing: an "instance" side keeps one row of sums per cloud, a "batch" side adds the partials of all clouds
     const epn_norm_pair_side *src[2] = {sa, sb};
@@ -902,8 +901,7 @@ static int norm_act2_bwd_apply_any(const void *xa, const void *xb, const void *d
     if (!xa || !xb || !dy || !sa->sums || !sb->sums || !dsums_a || !dsums_b) return EPN_ENULL;
     A.a.x = xa; A.b.x = xb; A.dy = dy; A.a.dsums = dsums_a; A.b.dsums = dsums_b; A.a.dx = dxa; A.b.dx = dxb;
     A.amax = reinterpret_cast<unsigned *>(amax_b);
-    if (bf16) EPN_LAUNCH(norm_act2_bwd_apply_kernel<__bf16>, grid, dim3(GT), 0, epn_stream(stream), A);
-    else EPN_LAUNCH(norm_act2_bwd_apply_kernel<float>, grid, dim3(GT), 0, epn_stream(stream), A);
+    EPN_LAUNCH_DT(bf16, norm_act2_bwd_apply_kernel, grid, dim3(GT), 0, epn_stream(stream), A);
     EPN_CHECK_LAUNCH();
     return 0;
 }
@@ -1006,6 +1004,23 @@ extern "C" size_t epn_stats_finish_workspace_bytes(int groups, long long blocks_
     return sizeof(float) * (size_t)groups * stats_finish_nz(blocks_per_group) * c * 2;
 }
 
+// optional first level of a reduction over block partials: more than 2048 blocks per group are first reduced 256 at a time
+// into the workspace, and (partials, blocks_per_group) then name that shorter list.  aux: how the launch is noted
+static int stats_prereduce(const float *&partials, long long &blocks_per_group, int groups, int c, void *workspace,
+                           size_t workspace_bytes, bool aux, hipStream_t st) {
+    const long long nz = stats_finish_nz(blocks_per_group);
+    if (!nz) return 0;
+    if (!workspace || workspace_bytes < epn_stats_finish_workspace_bytes(groups, blocks_per_group, c)) return EPN_EWORKSPACE;
+    float *part2 = static_cast<float *>(workspace);
+    ::epn::note_kernel(reinterpret_cast<const void *>(&stats_reduce_kernel), aux);
+    hipLaunchKernelGGL(stats_reduce_kernel, dim3(epn_cdiv(2 * c, 64), (unsigned)nz, groups), dim3(256), 0, st, partials,
+                       (int)blocks_per_group, c * 2, part2);
+    EPN_CHECK_LAUNCH();
+    partials = part2;
+    blocks_per_group = nz;
+    return 0;
+}
+
 extern "C" int epn_stats_finish(const float *partials, int groups, long long blocks_per_group, int c, float *sums,
                                 void *workspace, size_t workspace_bytes, epn_stream_t stream) {
     if (groups < 0 || blocks_per_group < 0 || c < 1 || blocks_per_group > 0x7fffffffLL) return EPN_EINVAL;
@@ -1014,16 +1029,7 @@ extern "C" int epn_stats_finish(const float *partials, int groups, long long blo
     if (groups == 0) return 0;
     if (!sums || (blocks_per_group && !partials)) return EPN_ENULL;
     hipStream_t st = epn_stream(stream);
-    const long long nz = stats_finish_nz(blocks_per_group);
-    if (nz) {
-        if (!workspace || workspace_bytes < epn_stats_finish_workspace_bytes(groups, blocks_per_group, c)) return EPN_EWORKSPACE;
-        float *part2 = static_cast<float *>(workspace);
-        EPN_LAUNCH(stats_reduce_kernel, dim3(epn_cdiv(2 * c, 64), (unsigned)nz, groups), dim3(256), 0, st, partials,
-                   (int)blocks_per_group, c * 2, part2);
-        EPN_CHECK_LAUNCH();
-        partials = part2;
-        blocks_per_group = nz;
-    }
+    if (const int rc = stats_prereduce(partials, blocks_per_group, groups, c, workspace, workspace_bytes, false, st)) return rc;
     EPN_LAUNCH(stats_finish_kernel, dim3(epn_cdiv(2 * c, 16), groups), dim3(256), 0, st, partials, (int)blocks_per_group,
                c * 2, sums);
     EPN_CHECK_LAUNCH();
@@ -1041,24 +1047,8 @@ extern "C" int epn_norm_bwd_finish(const float *partials, int groups, long long 
     if (groups == 0) return 0;
     if (!partials || !dsums) return EPN_ENULL;
     hipStream_t st = epn_stream(stream);
-    const long long nz = stats_finish_nz(blocks_per_group);
-    if (nz) {
-        if (!workspace || workspace_bytes < epn_stats_finish_workspace_bytes(groups, blocks_per_group, c)) return EPN_EWORKSPACE;
-        float *part2 = static_cast<float *>(workspace);
-        EPN_LAUNCH_AUX(stats_reduce_kernel, dim3(epn_cdiv(2 * c, 64), (unsigned)nz, groups), dim3(256), 0, st, partials,
-                       (int)blocks_per_group, c * 2, part2);
-        EPN_CHECK_LAUNCH();
-        partials = part2;
-        blocks_per_group = nz;
-    }
-    if (groups > 1) {                        // several groups accumulate with atomics; one group stores
-        if (dgamma) EPN_HIP(hipMemsetAsync(dgamma, 0, sizeof(float) * c, st));
-        if (dbeta) EPN_HIP(hipMemsetAsync(dbeta, 0, sizeof(float) * c, st));
-    }
-    EPN_LAUNCH(bwd_finish_kernel, dim3(epn_cdiv(c, 16), groups), dim3(256), 0, st, partials, (int)blocks_per_group, c, gamma,
-               dsums, dgamma, dbeta);
-    EPN_CHECK_LAUNCH();
-    return 0;
+    if (const int rc = stats_prereduce(partials, blocks_per_group, groups, c, workspace, workspace_bytes, true, st)) return rc;
+    return bwd_finish(partials, groups, (int)blocks_per_group, c, gamma, dsums, dgamma, dbeta, false, st);
 }
 
 extern "C" int epn_chan_stats_f32(const float *x_cl, int groups, long long rows, int c, float *sums, void *workspace,

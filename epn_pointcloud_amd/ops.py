@@ -1024,6 +1024,11 @@ def _tag_amax(t, amax):
         pass
 
 
+def _basis_rec(pts, na, c, device):
+    """Profiler record of one change of basis (see _run)."""
+    return "so3_basis", ("so3_basis", pts, c), 2.0 * pts * na * na * c, device
+
+
 def _basis_call(lib, src, M, basis, pts, c, in_spec, out_spec, dst, kind):
     if src.dtype != dst.dtype or src.dtype not in FEATURE_DTYPES:
         raise TypeError(f"so3_basis: {src.dtype} -> {dst.dtype}")
@@ -1078,7 +1083,7 @@ class FromSpectralFn(torch.autograd.Function):
         # + per-point partials of out's per-channel statistics, from the accumulators (epn_so3_basis_stats_*)
         part = torch.empty((b * p, c, 2), dtype=torch.float32, device=y.device)
         src = y.contiguous()
-        _run(("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * basis.na * basis.na * c, src.device), "so3_basis_stats",
+        _run(_basis_rec(b * p, basis.na, c, src.device), "so3_basis_stats",
              _entry(lib, "so3_basis_stats", src.dtype), ctypes.c_void_p(src.data_ptr()), _lib.dev_ptr(basis.U, "M"),
              _lib.dev_ptr(basis.blocks, "blocks", torch.int32), ctypes.c_longlong(b * p), basis.na, c, 1, 0,
              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(part.data_ptr()), _lib.stream_of(src))
@@ -1251,10 +1256,8 @@ def intra_so3conv_spectral(feats, W, intra_idx32, basis, pre_norm=None, pre_slop
         y = _norm_to_spectral_eval(f, pre_norm, pre_slope, basis, pre_part)
     elif pre_norm is not None:
         # the block's preceding norm + leaky_relu, folded into the transform's loads (training-mode statistics)
-        import torch.nn as nn
-        inst = isinstance(pre_norm, nn.InstanceNorm2d)
-        y, sums = NormToSpectralFn.apply(f, getattr(pre_norm, "weight", None), getattr(pre_norm, "bias", None), None,
-                                         inst, pre_norm.eps, pre_slope, basis, pre_part)
+        gamma, beta, inst, eps = _norm_params(pre_norm)
+        y, sums = NormToSpectralFn.apply(f, gamma, beta, None, inst, eps, pre_slope, basis, pre_part)
         _update_running_stats(pre_norm, sums, b * p * na)
     else:
         y = ToSpectralFn.apply(f, basis)
@@ -1278,49 +1281,90 @@ def norm_act_supported(c):
     return c >= 4 and c % 4 == 0 and c <= 1024 and 256 % (c // 4) == 0
 
 
+def _norm_params(norm):
+    """(gamma, beta, instance, eps) of an nn.BatchNorm2d / nn.InstanceNorm2d module, as the norm Functions take them."""
+    import torch.nn as nn
+    return getattr(norm, "weight", None), getattr(norm, "bias", None), isinstance(norm, nn.InstanceNorm2d), norm.eps
+
+
+def _groups_rows(instance, b, p, a):
+    """(statistics groups, rows per group) of a [b,c,p,a] tensor: one group per cloud for InstanceNorm, else one."""
+    return (b, p * a) if instance else (1, b * p * a)
+
+
+def _contiguous(t):
+    return t.contiguous() if t is not None else None
+
+
+def _zero_bias_grad(has_cb, c, device):
+    """Gradient of a conv_bias the normalisation cancels (see norm_act): exactly 0."""
+    return torch.zeros(c, dtype=torch.float32, device=device) if has_cb else None
+
+
+def _norm_act_forward(xc, stats, g, bt, residual, eps, slope, groups=1, drop=None, frozen=False):
+    """The single-tensor forward pass y = leaky_relu(norm(xc)) (+ residual) on channels-last xc.  stats: sums[groups][c][2] of
+    xc, or with frozen=True the stats[c][2] of _frozen_stats (epn_norm_act_frozen_fwd_*); drop = (rate, state): the mask is
+    drawn from the device's (seed, call) before the residual is added (epn_norm_act_dropout_fwd_*)."""
+    b, c, p, a = xc.shape
+    y = empty_cl(b, c, p, a, xc.device, xc.dtype)
+    r = cast_feats(to_cl(residual, "residual"), xc.dtype) if residual is not None else None
+    name, dims, extra = "norm_act_fwd", (groups, b * p * a // groups, c), ()
+    if frozen:
+        name, dims = "norm_act_frozen_fwd", (b * p * a, c)
+    elif drop is not None:
+        name, extra = "norm_act_dropout_fwd", (drop[0], _lib.dev_ptr(drop[1], "dropout state", torch.int64))
+    _lib.check(_entry(_lib.get_lib(), name, xc.dtype)(
+        _cl_ptr(xc), *dims, _lib.dev_ptr(stats, "stats" if frozen else "sums"), _lib.dev_ptr(g, "gamma"),
+        _lib.dev_ptr(bt, "beta"), _cl_ptr(r) if r is not None else ctypes.c_void_p(0), float(eps), float(slope), *extra,
+        _cl_ptr(y), _lib.stream_of(xc)), name)
+    return y
+
+
 class NormActFn(torch.autograd.Function):
     """y = leaky_relu(norm(x)) (+ residual) on a [b,c,p,a] tensor, norm = BatchNorm2d (groups=1, optional affine) or
     InstanceNorm2d(affine=False) (groups=b) -- `relu(norm(x))` of SPConvNets/utils/base_so3conv.py:116-126,52-62,208-211
     -- two streaming HIP passes forward, two backward (include/epn_so3conv.h, "block glue").
+    With rate, state (a checked dropout rate and dropout_state(device)): y = dropout(leaky_relu(norm(x)), rate) (+ residual,
+    added after the mask) -- `self.dropout(relu(norm(x)))` of base_so3conv.py:58-59 / 124-125, the skip branch of :205-211 --
+    in the same passes: the mask is generated in the kernels from the device's (seed, call) and regenerated, not stored, by
+    the backward; the forward keeps a copy of (seed, call) for it and advances `call` on the device.  Such a y leaves
+    WITHOUT a max|y| tag (two-piece fp16 GEMMs scan it: it is 1 / (1 - rate) above the undropped tensor).
     Returns (y, sums) with sums[g][c] = (sum x, sum x^2) for the caller's running-statistics update."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, residual, conv_bias, instance, eps, slope):
+    def forward(ctx, x, gamma, beta, residual, conv_bias, instance, eps, slope, rate=None, state=None):
         ctx.set_materialize_grads(False)   # else autograd zero-fills a gradient for every non-differentiable output, every step
-        lib = _lib.get_lib()
         xc = to_cl(x, "x")
         b, c, p, a = xc.shape
-        groups, rows = (b, p * a) if instance else (1, b * p * a)
-        st = _lib.stream_of(xc)
-        dt = xc.dtype
+        groups, rows = _groups_rows(instance, b, p, a)
         sums = _chan_stats(xc, groups, rows, c)
-        y = empty_cl(b, c, p, a, xc.device, dt)
-        g = gamma.contiguous() if gamma is not None else None
-        bt = beta.contiguous() if beta is not None else None
-        r = cast_feats(to_cl(residual, "residual"), dt) if residual is not None else None
-        _lib.check(_entry(lib, "norm_act_fwd", dt)(_cl_ptr(xc), groups, rows, c, _lib.dev_ptr(sums, "sums"),
-                                            _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"),
-                                            _cl_ptr(r) if r is not None else ctypes.c_void_p(0), float(eps),
-                                            float(slope), _cl_ptr(y), st), "norm_act_fwd")
-        ctx.save_for_backward(xc, sums, g, bt)
-        ctx.cfg = (groups, rows, c, float(eps), float(slope), residual is not None, conv_bias is not None)
+        g, bt = _contiguous(gamma), _contiguous(beta)
+        y = _norm_act_forward(xc, sums, g, bt, residual, eps, slope, groups, drop=None if rate is None else (rate, state))
+        saved = None
+        if rate is not None:       # a copy of (seed, call) for the backward; `call` advances on the device
+            saved = torch.empty_like(state)
+            _lib.check(_lib.get_lib().epn_dropout_state_next(_lib.dev_ptr(state, "dropout state", torch.int64),
+                                                             _lib.dev_ptr(saved, "saved state", torch.int64),
+                                                             _lib.stream_of(xc)), "dropout_state_next")
+        ctx.save_for_backward(xc, sums, g, bt, saved)
+        ctx.cfg = (groups, rows, c, float(eps), float(slope), residual is not None, conv_bias is not None, rate)
         ctx.mark_non_differentiable(sums)
         return y, sums
 
     @staticmethod
     def backward(ctx, grad_y, _grad_sums):
         if grad_y is None:
-            return (None,) * 8
-        xc, sums, g, bt = ctx.saved_tensors
-        groups, rows, c, eps, slope, has_res, has_cb = ctx.cfg
+            return (None,) * 10
+        xc, sums, g, bt, saved = ctx.saved_tensors
+        groups, rows, c, eps, slope, has_res, has_cb, rate = ctx.cfg
         dy = cast_feats(to_cl(grad_y, "grad_y"), xc.dtype)
-        dx, dg, db = _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, ctx.needs_input_grad[0])
-        # conv_bias (a bias the normalisation cancels, see norm_act): exact gradient = 0
-        dcb = torch.zeros(c, dtype=torch.float32, device=xc.device) if has_cb else None
-        return dx, dg, db, (dy if has_res else None), dcb, None, None, None
+        dx, dg, db = _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, ctx.needs_input_grad[0],
+                                        drop=None if rate is None else (rate, saved))
+        # the residual is never masked
+        return dx, dg, db, (dy if has_res else None), _zero_bias_grad(has_cb, c, xc.device), None, None, None, None, None
 
 
-# ---- dropout inside the norm passes: generator state, mask, Function ------------------------------------------------
+# ---- dropout inside the norm passes (NormActFn with a rate): generator state, mask ----------------------------------
 _DROPOUT_STATE = {}      # device index -> int64[2] device tensor (seed, call)
 
 
@@ -1380,53 +1424,6 @@ def _check_rate(rate):
     return rate
 
 
-class NormActDropoutFn(torch.autograd.Function):
-    """y = dropout(leaky_relu(norm(x)), rate) (+ residual, added after the mask) -- `self.dropout(relu(norm(x)))` of
-    SPConvNets/utils/base_so3conv.py:58-59 / 124-125, the skip branch of :205-211 -- in the same two streaming passes per
-    direction as NormActFn: the mask is generated in the kernels from the device's (seed, call) (dropout_state) and
-    regenerated, not stored, by the backward.  The forward keeps a copy of (seed, call) for its backward and advances `call`
-    on the device.  y leaves WITHOUT a max|y| tag (two-piece fp16 GEMMs scan it: it is 1 / (1 - rate) above the undropped
-    tensor).  Returns (y, sums) like NormActFn."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, residual, conv_bias, instance, eps, slope, rate, state):
-        ctx.set_materialize_grads(False)
-        lib = _lib.get_lib()
-        xc = to_cl(x, "x")
-        b, c, p, a = xc.shape
-        groups, rows = (b, p * a) if instance else (1, b * p * a)
-        st = _lib.stream_of(xc)
-        dt = xc.dtype
-        sums = _chan_stats(xc, groups, rows, c)
-        y = empty_cl(b, c, p, a, xc.device, dt)
-        g = gamma.contiguous() if gamma is not None else None
-        bt = beta.contiguous() if beta is not None else None
-        r = cast_feats(to_cl(residual, "residual"), dt) if residual is not None else None
-        sp = _lib.dev_ptr(state, "dropout state", torch.int64)
-        _lib.check(_entry(lib, "norm_act_dropout_fwd", dt)(_cl_ptr(xc), groups, rows, c, _lib.dev_ptr(sums, "sums"),
-                                                           _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"),
-                                                           _cl_ptr(r) if r is not None else ctypes.c_void_p(0), float(eps),
-                                                           float(slope), rate, sp, _cl_ptr(y), st), "norm_act_dropout_fwd")
-        saved = torch.empty_like(state)
-        _lib.check(lib.epn_dropout_state_next(sp, _lib.dev_ptr(saved, "saved state", torch.int64), st), "dropout_state_next")
-        ctx.save_for_backward(xc, sums, g, bt, saved)
-        ctx.cfg = (groups, rows, c, float(eps), float(slope), residual is not None, conv_bias is not None, rate)
-        ctx.mark_non_differentiable(sums)
-        return y, sums
-
-    @staticmethod
-    def backward(ctx, grad_y, _grad_sums):
-        if grad_y is None:
-            return (None,) * 10
-        xc, sums, g, bt, saved = ctx.saved_tensors
-        groups, rows, c, eps, slope, has_res, has_cb, rate = ctx.cfg
-        dy = cast_feats(to_cl(grad_y, "grad_y"), xc.dtype)
-        dx, dg, db = _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, ctx.needs_input_grad[0],
-                                        drop=(rate, saved))
-        dcb = torch.zeros(c, dtype=torch.float32, device=xc.device) if has_cb else None
-        return dx, dg, db, (dy if has_res else None), dcb, None, None, None, None, None      # the residual is never masked
-
-
 def _pair_side(sums, g, bt, eps, instance):
     sd = _lib.NormPairSide()
     sd.sums = _lib.dev_ptr(sums, "sums")
@@ -1434,6 +1431,32 @@ def _pair_side(sums, g, bt, eps, instance):
     sd.beta = _lib.dev_ptr(bt, "beta")
     sd.eps, sd.instance = float(eps), int(instance)
     return sd
+
+
+def _pair_inputs(xa, xb, ga, ba, eps_a, inst_a, inst_b, part_a, part_b):
+    """Input preparation of the pair passes: both tensors channels-last in xa's dtype, side a's statistics (from part_a when
+    given: one block per point) and side descriptor, side b's statistics (from part_b when given; inst_b None: a frozen
+    side, which has none).  -> (xac, xbc, sums_a, sums_b, side a)."""
+    xac = to_cl(xa, "xa")
+    xbc = to_cl(xb, "xb")
+    if xbc.dtype != xac.dtype:
+        xbc, part_b = cast_feats(xbc, xac.dtype), None      # statistics of the values the kernel will read
+    b, c, p, a = xac.shape
+    sums_a = _stats(xac, *_groups_rows(inst_a, b, p, a), c, part_a, a)
+    sums_b = _stats(xbc, *_groups_rows(inst_b, b, p, a), c, part_b) if inst_b is not None else None
+    return xac, xbc, sums_a, sums_b, _pair_side(sums_a, ga, ba, eps_a, inst_a)
+
+
+def _pair_call(name, args, st, tag=None):
+    """epn_norm_act_pair_<name>(*args, st) -- or, when `tag` (the output that two-piece fp16 GEMMs will read) asks for it, the
+    _amax entry with its trailing pointer: max|tag| from this pass, remembered on the tensor."""
+    lib = _lib.get_lib()
+    if tag is not None and gemm.f16x2_on(tag):
+        amax = torch.empty(1, dtype=torch.float32, device=tag.device)
+        _lib.check(getattr(lib, f"epn_norm_act_pair_{name}_amax")(*args, amax.data_ptr(), st), f"norm_act_pair_{name}_amax")
+        _tag_amax(tag, amax)
+    else:
+        _lib.check(getattr(lib, f"epn_norm_act_pair_{name}")(*args, st), f"norm_act_pair_{name}")
 
 
 class NormActPairFn(torch.autograd.Function):
@@ -1446,29 +1469,15 @@ class NormActPairFn(torch.autograd.Function):
     def forward(ctx, xa, xb, gamma_a, beta_a, gamma_b, beta_b, conv_bias_b, inst_a, inst_b, eps_a, eps_b, slope,
                 part_b=None, part_a=None):
         ctx.set_materialize_grads(False)   # else autograd zero-fills a gradient for every non-differentiable output, every step
-        lib = _lib.get_lib()
-        xac = to_cl(xa, "xa")
-        xbc = to_cl(xb, "xb")
-        if xbc.dtype != xac.dtype:
-            xbc, part_b = cast_feats(xbc, xac.dtype), None      # statistics of the values the kernel will read
+        ga, ba, gb, bb = (_contiguous(t) for t in (gamma_a, beta_a, gamma_b, beta_b))
+        xac, xbc, sums_a, sums_b, sa = _pair_inputs(xa, xb, ga, ba, eps_a, inst_a, bool(inst_b), part_a, part_b)
         b, c, p, a = xac.shape
         rows = p * a
-        sums_a = _stats(xac, b if inst_a else 1, rows if inst_a else b * rows, c, part_a, a)   # one block per point
-        sums_b = _stats(xbc, b if inst_b else 1, rows if inst_b else b * rows, c, part_b)
-        ga, ba = (t.contiguous() if t is not None else None for t in (gamma_a, beta_a))
-        gb, bb = (t.contiguous() if t is not None else None for t in (gamma_b, beta_b))
+        sb = _pair_side(sums_b, gb, bb, eps_b, inst_b)
         y = empty_cl(b, c, p, a, xac.device, xac.dtype)
-        sa, sb = _pair_side(sums_a, ga, ba, eps_a, inst_a), _pair_side(sums_b, gb, bb, eps_b, inst_b)
-        if gemm.f16x2_on(y):       # the block output is the next block's GEMM operand source: its maximum from this pass
-            amax = torch.empty(1, dtype=torch.float32, device=y.device)
-            _lib.check(lib.epn_norm_act_pair_fwd_amax(_cl_ptr(xac), _cl_ptr(xbc), b, rows, c, ctypes.byref(sa), ctypes.byref(sb),
-                                                      float(slope), _cl_ptr(y), 0, amax.data_ptr(), _lib.stream_of(xac)),
-                       "norm_act_pair_fwd_amax")
-            _tag_amax(y, amax)
-        else:
-            _lib.check(lib.epn_norm_act_pair_fwd(_cl_ptr(xac), _cl_ptr(xbc), b, rows, c, ctypes.byref(sa), ctypes.byref(sb),
-                                                 float(slope), _cl_ptr(y), int(xac.dtype == torch.bfloat16),
-                                                 _lib.stream_of(xac)), "norm_act_pair_fwd")
+        # the block output is the next block's GEMM operand source: its maximum from this pass
+        _pair_call("fwd", (_cl_ptr(xac), _cl_ptr(xbc), b, rows, c, ctypes.byref(sa), ctypes.byref(sb), float(slope), _cl_ptr(y),
+                           int(xac.dtype == torch.bfloat16)), _lib.stream_of(xac), tag=y)
         ctx.save_for_backward(xac, xbc, sums_a, sums_b, ga, ba, gb, bb)
         ctx.cfg = (b, rows, c, bool(inst_a), bool(inst_b), float(eps_a), float(eps_b), float(slope), conv_bias_b is not None)
         ctx.mark_non_differentiable(sums_a, sums_b)
@@ -1486,38 +1495,23 @@ class NormActPairFn(torch.autograd.Function):
         bf = int(xac.dtype == torch.bfloat16)
         sa, sb = _pair_side(sums_a, ga, ba, eps_a, inst_a), _pair_side(sums_b, gb, bb, eps_b, inst_b)
         dsa, dsb = torch.empty_like(sums_a), torch.empty_like(sums_b)
-        f32 = dict(dtype=torch.float32, device=dev)
-        dga = torch.empty(c, **f32) if ga is not None else None
-        dba = torch.empty(c, **f32) if ba is not None else None
-        dgb = torch.empty(c, **f32) if gb is not None else None
-        dbb = torch.empty(c, **f32) if bb is not None else None
+        dga, dba, dgb, dbb = (torch.empty(c, dtype=torch.float32, device=dev) if t is not None else None
+                              for t in (ga, ba, gb, bb))
         ws, wsp, wsn = _ws(lib.epn_norm_pair_workspace_bytes(b, rows, c), dev)
         st = _lib.stream_of(xac)
-        _lib.check(lib.epn_norm_act_pair_bwd_reduce(_cl_ptr(xac), _cl_ptr(xbc), _cl_ptr(dy), b, rows, c, ctypes.byref(sa),
-                                                    ctypes.byref(sb), slope, _lib.dev_ptr(dsa, "dsums_a"),
-                                                    _lib.dev_ptr(dga, "dgamma_a"), _lib.dev_ptr(dba, "dbeta_a"),
-                                                    _lib.dev_ptr(dsb, "dsums_b"), _lib.dev_ptr(dgb, "dgamma_b"),
-                                                    _lib.dev_ptr(dbb, "dbeta_b"), wsp, wsn, bf, st),
-                   "norm_act_pair_bwd_reduce")
+        common = (_cl_ptr(xac), _cl_ptr(xbc), _cl_ptr(dy), b, rows, c, ctypes.byref(sa), ctypes.byref(sb), slope)
+        _pair_call("bwd_reduce", (*common, _lib.dev_ptr(dsa, "dsums_a"), _lib.dev_ptr(dga, "dgamma_a"),
+                                  _lib.dev_ptr(dba, "dbeta_a"), _lib.dev_ptr(dsb, "dsums_b"), _lib.dev_ptr(dgb, "dgamma_b"),
+                                  _lib.dev_ptr(dbb, "dbeta_b"), wsp, wsn, bf), st)
         dxa = torch.empty_like(xac) if ctx.needs_input_grad[0] else None
         dxb = torch.empty_like(xbc) if ctx.needs_input_grad[1] else None
         if dxa is not None or dxb is not None:
             pa = _cl_ptr(dxa) if dxa is not None else ctypes.c_void_p(0)
             pb = _cl_ptr(dxb) if dxb is not None else ctypes.c_void_p(0)
-            if dxb is not None and gemm.f16x2_on(dxb):      # side b's gradient feeds the skip convolution's backward GEMMs
-                amax = torch.empty(1, dtype=torch.float32, device=dxb.device)
-                _lib.check(lib.epn_norm_act_pair_bwd_apply_amax(_cl_ptr(xac), _cl_ptr(xbc), _cl_ptr(dy), b, rows, c, ctypes.byref(sa),
-                                                                ctypes.byref(sb), slope, _lib.dev_ptr(dsa, "dsums_a"),
-                                                                _lib.dev_ptr(dsb, "dsums_b"), pa, pb, bf, amax.data_ptr(),
-                                                                _lib.stream_of(xac)), "norm_act_pair_bwd_apply_amax")
-                _tag_amax(dxb, amax)
-            else:
-                _lib.check(lib.epn_norm_act_pair_bwd_apply(_cl_ptr(xac), _cl_ptr(xbc), _cl_ptr(dy), b, rows, c, ctypes.byref(sa),
-                                                           ctypes.byref(sb), slope, _lib.dev_ptr(dsa, "dsums_a"),
-                                                           _lib.dev_ptr(dsb, "dsums_b"), pa, pb, bf,
-                                                           _lib.stream_of(xac)), "norm_act_pair_bwd_apply")
-        dcb = torch.zeros(c, **f32) if has_cb else None       # a bias the normalisation cancels: exact gradient 0
-        return dxa, dxb, dga, dba, dgb, dbb, dcb, None, None, None, None, None, None, None
+            # side b's gradient feeds the skip convolution's backward GEMMs
+            _pair_call("bwd_apply", (*common, _lib.dev_ptr(dsa, "dsums_a"), _lib.dev_ptr(dsb, "dsums_b"), pa, pb, bf),
+                       _lib.stream_of(xac), tag=dxb)
+        return dxa, dxb, dga, dba, dgb, dbb, _zero_bias_grad(has_cb, c, dev), None, None, None, None, None, None, None
 
 
 def norm_act_pair(xa, norm_a, xb, norm_b, conv_bias_b=None, slope=0.01, part_b=None, part_a=None):
@@ -1526,11 +1520,8 @@ def norm_act_pair(xa, norm_a, xb, norm_b, conv_bias_b=None, slope=0.01, part_b=N
     conv_bias_b: bias of the convolution that produced xb, NOT added to xb (see norm_act).  part_b: block partials of xb's
     per-channel statistics from the epilogue of the GEMM that produced it (conv1x1(..., col_stats=True)); part_a: per-point
     partials of xa's from the inverse basis change (intra_so3conv(..., out_stats=True))."""
-    import torch.nn as nn
-    ia, ib = isinstance(norm_a, nn.InstanceNorm2d), isinstance(norm_b, nn.InstanceNorm2d)
-    y, sums_a, sums_b = NormActPairFn.apply(xa, xb, getattr(norm_a, "weight", None), getattr(norm_a, "bias", None),
-                                            getattr(norm_b, "weight", None), getattr(norm_b, "bias", None), conv_bias_b,
-                                            ia, ib, norm_a.eps, norm_b.eps, slope, part_b, part_a)
+    (ga, ba, ia, eps_a), (gb, bb, ib, eps_b) = _norm_params(norm_a), _norm_params(norm_b)
+    y, sums_a, sums_b = NormActPairFn.apply(xa, xb, ga, ba, gb, bb, conv_bias_b, ia, ib, eps_a, eps_b, slope, part_b, part_a)
     n = xa.shape[0] * xa.shape[2] * xa.shape[3]
     _update_running_stats(norm_a, sums_a, n)
     _update_running_stats(norm_b, sums_b, n, conv_bias_b)
@@ -1568,31 +1559,75 @@ def _stats(xc, groups, rows, c, part=None, block_rows=32):
     return sums if sums is not None else _chan_stats(xc, groups, rows, c)
 
 
-def _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, need_dx, drop=None):
-    """Backward of y = leaky(norm(x)): (dx, dgamma, dbeta) from x, dy and the forward statistics (two streaming passes).
-    drop = (rate, saved state) of a dropout forward: both passes regenerate its mask and read dy * m / (1 - rate) for dy."""
+def _drop_args(drop):
+    return float(drop[0]), _lib.dev_ptr(drop[1], "dropout state", torch.int64)
+
+
+def _norm_bwd_reduce(xc, dy, sums, g, bt, groups, rows, c, eps, slope, drop=None, part=None):
+    """First backward pass of y = leaky(norm(x)): (dsums, dgamma, dbeta).  A streaming pass over x and dy
+    (epn_norm_act[_dropout]_bwd_reduce_*), or, with part = the per-point partials the inverse basis change that produced dy
+    wrote from its accumulators (epn_so3_basis_dstats_*), only their finishing kernel (epn_norm_bwd_finish)."""
     lib = _lib.get_lib()
-    st = _lib.stream_of(xc)
-    reduce_name, apply_name, extra = "norm_act_bwd_reduce", "norm_act_bwd_apply", ()
-    if drop is not None:
-        reduce_name, apply_name = "norm_act_dropout_bwd_reduce", "norm_act_dropout_bwd_apply"
-        extra = (float(drop[0]), _lib.dev_ptr(drop[1], "dropout state", torch.int64))
     dsums = torch.empty_like(sums)
     dg = torch.empty(c, dtype=torch.float32, device=xc.device) if g is not None else None
     db = torch.empty(c, dtype=torch.float32, device=xc.device) if bt is not None else None
-    gp, bp = _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta")
+    outs = (_lib.dev_ptr(dsums, "dsums"), _lib.dev_ptr(dg, "dgamma"), _lib.dev_ptr(db, "dbeta"))
+    if part is not None:
+        bpg = part.shape[0] // groups
+        ws, wsp, wsn = _ws(lib.epn_stats_finish_workspace_bytes(groups, bpg, c), xc.device)
+        _lib.check(lib.epn_norm_bwd_finish(part.data_ptr(), groups, ctypes.c_longlong(bpg), c, _lib.dev_ptr(g, "gamma"), *outs,
+                                           wsp, wsn, _lib.stream_of(xc)), "norm_bwd_finish")
+        return dsums, dg, db
+    name, extra = ("norm_act_bwd_reduce", ()) if drop is None else ("norm_act_dropout_bwd_reduce", _drop_args(drop))
     ws, wsp, wsn = _ws(lib.epn_norm_workspace_bytes(groups, rows, c), xc.device)
-    _lib.check(_entry(lib, reduce_name, xc.dtype)(_cl_ptr(xc), _cl_ptr(dy), groups, rows, c,
-                                               _lib.dev_ptr(sums, "sums"), gp, bp, eps, slope, *extra,
-                                               _lib.dev_ptr(dsums, "dsums"), _lib.dev_ptr(dg, "dgamma"),
-                                               _lib.dev_ptr(db, "dbeta"), wsp, wsn, st), reduce_name)
-    dx = None
-    if need_dx:
-        dx = torch.empty_like(xc)
-        _lib.check(_entry(lib, apply_name, xc.dtype)(_cl_ptr(xc), _cl_ptr(dy), groups, rows, c,
-                                                  _lib.dev_ptr(sums, "sums"), _lib.dev_ptr(dsums, "dsums"), gp, bp,
-                                                  eps, slope, *extra, _cl_ptr(dx), st), apply_name)
+    _lib.check(_entry(lib, name, xc.dtype)(_cl_ptr(xc), _cl_ptr(dy), groups, rows, c, _lib.dev_ptr(sums, "sums"),
+                                           _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), eps, slope, *extra, *outs,
+                                           wsp, wsn, _lib.stream_of(xc)), name)
+    return dsums, dg, db
+
+
+def _norm_bwd_apply(xc, dy, sums, g, bt, groups, rows, c, eps, slope, dsums, drop=None, want_amax=False):
+    """Second backward pass: dx from x, dy, the forward statistics and dsums.  want_amax: dx is the narrow operand of
+    two-piece fp16 GEMMs (an inter convolution's output gradient): its maximum from this pass, remembered on the tensor."""
+    lib = _lib.get_lib()
+    dx = torch.empty_like(xc)
+    name, extra = ("norm_act_bwd_apply", ()) if drop is None else ("norm_act_dropout_bwd_apply", _drop_args(drop))
+    args = (_cl_ptr(xc), _cl_ptr(dy), groups, rows, c, _lib.dev_ptr(sums, "sums"), _lib.dev_ptr(dsums, "dsums"),
+            _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), eps, slope, *extra, _cl_ptr(dx))
+    if want_amax and gemm.f16x2_on(dx):
+        amax = torch.empty(1, dtype=torch.float32, device=dx.device)
+        _lib.check(lib.epn_norm_act_bwd_apply_amax_f32(*args, amax.data_ptr(), _lib.stream_of(xc)), "norm_act_bwd_apply_amax")
+        _tag_amax(dx, amax)
+    else:
+        _lib.check(_entry(lib, name, xc.dtype)(*args, _lib.stream_of(xc)), name)
+    return dx
+
+
+def _norm_act_backward(xc, dy, sums, g, bt, groups, rows, c, eps, slope, need_dx, drop=None):
+    """Backward of y = leaky(norm(x)): (dx, dgamma, dbeta) from x, dy and the forward statistics (two streaming passes).
+    drop = (rate, saved state) of a dropout forward: both passes regenerate its mask and read dy * m / (1 - rate) for dy."""
+    dsums, dg, db = _norm_bwd_reduce(xc, dy, sums, g, bt, groups, rows, c, eps, slope, drop)
+    dx = _norm_bwd_apply(xc, dy, sums, g, bt, groups, rows, c, eps, slope, dsums, drop) if need_dx else None
     return dx, dg, db
+
+
+def _norm_to_spectral(xc, basis, name, stats_args, g, bt, eps, slope):
+    """y = ToSpectral(leaky_relu(norm(xc))) through epn_so3_basis_<name>_*, the norm applied as the kernel loads its rows.
+    stats_args: the entry's statistics arguments (batch: sums, groups, points per cloud; frozen: stats)."""
+    lib = _lib.get_lib()
+    b, c, p, na = xc.shape
+    y = torch.empty(na * b * p * c, dtype=xc.dtype, device=xc.device)
+    rec = _basis_rec(b * p, na, c, xc.device)
+    args = (_cl_ptr(xc), _lib.dev_ptr(basis.Ut, "M"), _lib.dev_ptr(basis.blocks, "blocks", torch.int32),
+            ctypes.c_longlong(b * p), na, c, 1, ctypes.c_void_p(y.data_ptr()), *stats_args, _lib.dev_ptr(g, "gamma"),
+            _lib.dev_ptr(bt, "beta"), float(eps), float(slope))
+    if name == "so3_basis_norm" and gemm.f16x2_on(y):       # + max|y| for the two-piece GEMMs that read it (see _basis_call)
+        amax = torch.empty(1, dtype=torch.float32, device=y.device)
+        _run(rec, name + "_amax", lib.epn_so3_basis_norm_amax_split_f32, *args, amax.data_ptr(), _lib.stream_of(xc))
+        _tag_amax(y, amax)
+    else:
+        _run(rec, name, _entry(lib, name, xc.dtype), *args, _lib.stream_of(xc))
+    return y
 
 
 class NormToSpectralFn(torch.autograd.Function):
@@ -1603,24 +1638,13 @@ class NormToSpectralFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, conv_bias, instance, eps, slope, basis, part=None):
         ctx.set_materialize_grads(False)   # else autograd zero-fills a gradient for every non-differentiable output, every step
-        lib = _lib.get_lib()
         xc = to_cl(x, "x")
         b, c, p, na = xc.shape
-        groups, rows = (b, p * na) if instance else (1, b * p * na)
+        groups, rows = _groups_rows(instance, b, p, na)
         sums = _stats(xc, groups, rows, c, part)           # part: block partials from the epilogue of x's producer
-        g = gamma.contiguous() if gamma is not None else None
-        bt = beta.contiguous() if beta is not None else None
-        y = torch.empty(na * b * p * c, dtype=xc.dtype, device=xc.device)
-        rec = ("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, xc.device)
-        args = (_cl_ptr(xc), _lib.dev_ptr(basis.Ut, "M"), _lib.dev_ptr(basis.blocks, "blocks", torch.int32),
-                ctypes.c_longlong(b * p), na, c, 1, ctypes.c_void_p(y.data_ptr()), _lib.dev_ptr(sums, "sums"), groups,
-                ctypes.c_longlong(p), _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), float(eps), float(slope))
-        if gemm.f16x2_on(y):                                 # + max|y| for the two-piece GEMMs that read it (see _basis_call)
-            amax = torch.empty(1, dtype=torch.float32, device=y.device)
-            _run(rec, "so3_basis_norm_amax", lib.epn_so3_basis_norm_amax_split_f32, *args, amax.data_ptr(), _lib.stream_of(xc))
-            _tag_amax(y, amax)
-        else:
-            _run(rec, "so3_basis_norm", _entry(lib, "so3_basis_norm", xc.dtype), *args, _lib.stream_of(xc))
+        g, bt = _contiguous(gamma), _contiguous(beta)
+        y = _norm_to_spectral(xc, basis, "so3_basis_norm", (_lib.dev_ptr(sums, "sums"), groups, ctypes.c_longlong(p)),
+                              g, bt, eps, slope)
         ctx.save_for_backward(xc, sums, g, bt)
         ctx.basis = basis
         ctx.cfg = (groups, rows, c, float(eps), float(slope), conv_bias is not None, (b, c, p, na))
@@ -1635,46 +1659,25 @@ class NormToSpectralFn(torch.autograd.Function):
         xc, sums, g, bt = ctx.saved_tensors
         groups, rows, c, eps, slope, has_cb, (b, _, p, na) = ctx.cfg
         gf = empty_cl(b, c, p, na, gy.device, xc.dtype)
-        fused = (ab("EPN_NORM_BWD_EPILOGUE") == "1" and ctx.needs_input_grad[0]
-                 and xc.numel() * xc.element_size() < 0x7fffff00 and b * p < (1 << 24))
-        if fused:
+        gyc = cast_feats(gy.contiguous(), xc.dtype)
+        norm = (xc, gf, sums, g, bt, groups, rows, c, eps, slope)
+        if (ab("EPN_NORM_BWD_EPILOGUE") == "1" and ctx.needs_input_grad[0]
+                and xc.numel() * xc.element_size() < 0x7fffff00 and b * p < (1 << 24)):
             # the norm's backward reduction from the accumulators of the inverse basis change that produces its output gradient
             # (epn_so3_basis_dstats_*): no norm_act_bwd_reduce pass over x and dy
-            gyc = cast_feats(gy.contiguous(), xc.dtype)
             pd = torch.empty((b * p, c, 2), dtype=torch.float32, device=gy.device)
-            _run(("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, gy.device), "so3_basis_dstats",
+            _run(_basis_rec(b * p, na, c, gy.device), "so3_basis_dstats",
                  _entry(lib, "so3_basis_dstats", xc.dtype), ctypes.c_void_p(gyc.data_ptr()), _lib.dev_ptr(ctx.basis.U, "M"),
                  _lib.dev_ptr(ctx.basis.blocks, "blocks", torch.int32), ctypes.c_longlong(b * p), na, c, _cl_ptr(gf), _cl_ptr(xc),
                  _lib.dev_ptr(sums, "sums"), groups, ctypes.c_longlong(p), _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"),
                  float(eps), float(slope), pd.data_ptr(), _lib.stream_of(gf))
-            dsums = torch.empty_like(sums)
-            dg = torch.empty(c, dtype=torch.float32, device=gy.device) if g is not None else None
-            db = torch.empty(c, dtype=torch.float32, device=gy.device) if bt is not None else None
-            bpg = b * p // groups
-            ws, wsp, wsn = _ws(lib.epn_stats_finish_workspace_bytes(groups, bpg, c), gy.device)
-            _lib.check(lib.epn_norm_bwd_finish(pd.data_ptr(), groups, ctypes.c_longlong(bpg), c, _lib.dev_ptr(g, "gamma"),
-                                               _lib.dev_ptr(dsums, "dsums"), _lib.dev_ptr(dg, "dgamma"), _lib.dev_ptr(db, "dbeta"),
-                                               wsp, wsn, _lib.stream_of(gf)), "norm_bwd_finish")
-            dx = torch.empty_like(xc)
-            if gemm.f16x2_on(dx):      # dx is the inter convolution's output gradient: the narrow operand of two backward GEMMs
-                amax = torch.empty(1, dtype=torch.float32, device=dx.device)
-                _lib.check(lib.epn_norm_act_bwd_apply_amax_f32(_cl_ptr(xc), _cl_ptr(gf), groups, rows, c,
-                                                               _lib.dev_ptr(sums, "sums"), _lib.dev_ptr(dsums, "dsums"),
-                                                               _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), eps, slope,
-                                                               _cl_ptr(dx), amax.data_ptr(), _lib.stream_of(gf)),
-                           "norm_act_bwd_apply_amax")
-                _tag_amax(dx, amax)
-            else:
-                _lib.check(_entry(lib, "norm_act_bwd_apply", xc.dtype)(_cl_ptr(xc), _cl_ptr(gf), groups, rows, c,
-                                                                      _lib.dev_ptr(sums, "sums"), _lib.dev_ptr(dsums, "dsums"),
-                                                                      _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), eps, slope,
-                                                                      _cl_ptr(dx), _lib.stream_of(gf)), "norm_act_bwd_apply")
-            dcb = torch.zeros(c, dtype=torch.float32, device=xc.device) if has_cb else None
-            return dx, dg, db, dcb, None, None, None, None, None
-        _basis_call(lib, cast_feats(gy.contiguous(), xc.dtype), ctx.basis.U, ctx.basis, b * p, c, 1, 0, gf, "so3_basis")
-        dx, dg, db = _norm_act_backward(xc, gf, sums, g, bt, groups, rows, c, eps, slope, ctx.needs_input_grad[0])
-        dcb = torch.zeros(c, dtype=torch.float32, device=xc.device) if has_cb else None
-        return dx, dg, db, dcb, None, None, None, None, None
+            dsums, dg, db = _norm_bwd_reduce(*norm, part=pd)
+            # dx is the inter convolution's output gradient: the narrow operand of two backward GEMMs
+            dx = _norm_bwd_apply(*norm, dsums, want_amax=True)
+        else:
+            _basis_call(lib, gyc, ctx.basis.U, ctx.basis, b * p, c, 1, 0, gf, "so3_basis")
+            dx, dg, db = _norm_act_backward(*norm, ctx.needs_input_grad[0])
+        return dx, dg, db, _zero_bias_grad(has_cb, c, xc.device), None, None, None, None, None
 
 
 def _update_running_stats(norm, sums, n, conv_bias=None):
@@ -1717,16 +1720,10 @@ def norm_act(x, norm, residual=None, slope=0.01, conv_bias=None, *, dropout=0.0)
     per-channel mean, so norm(x + b) == norm(x) and d/db == 0 exactly: the add (a full read + write of the tensor) and
     the bias-gradient reduction are skipped, only BatchNorm's running_mean needs b.
     dropout (keyword only): rate of an nn.Dropout applied to leaky_relu(norm(x)) BEFORE the residual is added, 0 < rate < 1 (or 0.0: none),
-    drawn from dropout_state(x.device) inside the same passes (NormActDropoutFn); the running statistics are those of x."""
-    import torch.nn as nn
-    instance = isinstance(norm, nn.InstanceNorm2d)
-    gamma = getattr(norm, "weight", None)
-    beta = getattr(norm, "bias", None)
-    if dropout == 0.0:
-        y, sums = NormActFn.apply(x, gamma, beta, residual, conv_bias, instance, norm.eps, slope)
-    else:
-        y, sums = NormActDropoutFn.apply(x, gamma, beta, residual, conv_bias, instance, norm.eps, slope,
-                                         _check_rate(dropout), dropout_state(x.device))
+    drawn from dropout_state(x.device) inside the same passes (NormActFn with a rate); the running statistics are those of x."""
+    gamma, beta, instance, eps = _norm_params(norm)
+    drop = (None, None) if dropout == 0.0 else (_check_rate(dropout), dropout_state(x.device))
+    y, sums = NormActFn.apply(x, gamma, beta, residual, conv_bias, instance, eps, slope, *drop)
     _update_running_stats(norm, sums, x.shape[0] * x.shape[2] * x.shape[3], conv_bias)
     return y
 
@@ -1791,23 +1788,12 @@ def norm_act_eval(x, norm, residual=None, slope=0.01, conv_bias=None):
     kind = _eval_kind(norm)
     _forward_only("norm_act_eval", x, residual, conv_bias, *norm.parameters())
     if kind == "batch":
-        import torch.nn as nn
+        gamma, beta, instance, eps = _norm_params(norm)
         with torch.no_grad():
-            return NormActFn.apply(x, getattr(norm, "weight", None), getattr(norm, "bias", None), residual, conv_bias,
-                                   isinstance(norm, nn.InstanceNorm2d), norm.eps, slope)[0]
-    lib = _lib.get_lib()
+            return NormActFn.apply(x, gamma, beta, residual, conv_bias, instance, eps, slope)[0]
     xc = to_cl(x, "x")
-    b, c, p, a = xc.shape
-    dt = xc.dtype
     stats = _frozen_stats(norm, conv_bias)
-    g, bt = _affine(norm)
-    y = empty_cl(b, c, p, a, xc.device, dt)
-    r = cast_feats(to_cl(residual, "residual"), dt) if residual is not None else None
-    _lib.check(_entry(lib, "norm_act_frozen_fwd", dt)(_cl_ptr(xc), b * p * a, c, _lib.dev_ptr(stats, "stats"),
-                                                      _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"),
-                                                      _cl_ptr(r) if r is not None else ctypes.c_void_p(0), float(norm.eps),
-                                                      float(slope), _cl_ptr(y), _lib.stream_of(xc)), "norm_act_frozen_fwd")
-    return y
+    return _norm_act_forward(xc, stats, *_affine(norm), residual, norm.eps, slope, frozen=True)
 
 
 def norm_act_pair_eval(xa, norm_a, xb, norm_b, conv_bias_b=None, slope=0.01, part_b=None, part_a=None):
@@ -1815,34 +1801,25 @@ def norm_act_pair_eval(xa, norm_a, xb, norm_b, conv_bias_b=None, slope=0.01, par
     statistics (a separable block's InstanceNorm2d: statistics of xa, from part_a when given).  norm_b: an nn.BatchNorm2d with
     running statistics -- frozen side, epn_norm_act_pair_frozen_fwd; conv_bias_b goes into its mean as in norm_act_eval -- or a
     norm without them: the training forward of norm_act_pair (statistics from part_b when given), no running update."""
-    import torch.nn as nn
     ka, kb = _eval_kind(norm_a), _eval_kind(norm_b)
     if ka != "batch":
         raise TypeError("norm_act_pair_eval: side a takes a norm without running statistics")
     _forward_only("norm_act_pair_eval", xa, xb, conv_bias_b, *norm_a.parameters(), *norm_b.parameters())
-    ia = isinstance(norm_a, nn.InstanceNorm2d)
+    (ga, ba, ia, eps_a), (gb, bb, ib, eps_b) = _norm_params(norm_a), _norm_params(norm_b)
     if kb == "batch":
         with torch.no_grad():
-            return NormActPairFn.apply(xa, xb, getattr(norm_a, "weight", None), getattr(norm_a, "bias", None),
-                                       getattr(norm_b, "weight", None), getattr(norm_b, "bias", None), conv_bias_b, ia,
-                                       isinstance(norm_b, nn.InstanceNorm2d), norm_a.eps, norm_b.eps, slope, part_b, part_a)[0]
-    lib = _lib.get_lib()
-    xac = to_cl(xa, "xa")
-    xbc = cast_feats(to_cl(xb, "xb"), xac.dtype)
+            return NormActPairFn.apply(xa, xb, ga, ba, gb, bb, conv_bias_b, ia, ib, eps_a, eps_b, slope, part_b, part_a)[0]
+    (ga, ba), (gb, bb) = _affine(norm_a), _affine(norm_b)
+    # (sa holds raw pointers to sums_a, ga, ba: they stay bound until the launch below)
+    xac, xbc, sums_a, _, sa = _pair_inputs(xa, xb, ga, ba, eps_a, ia, None, part_a, None)
     b, c, p, a = xac.shape
-    rows = p * a
-    sums_a = _stats(xac, b if ia else 1, rows if ia else b * rows, c, part_a, a)
-    ga, ba = _affine(norm_a)
-    gb, bb = _affine(norm_b)
-    sa = _pair_side(sums_a, ga, ba, norm_a.eps, ia)
     stats_b = _frozen_stats(norm_b, conv_bias_b)
     sb = _lib.NormPairFrozenSide()
     sb.stats, sb.gamma, sb.beta = _lib.dev_ptr(stats_b, "stats"), _lib.dev_ptr(gb, "gamma"), _lib.dev_ptr(bb, "beta")
-    sb.eps, sb.frozen = float(norm_b.eps), 1
+    sb.eps, sb.frozen = float(eps_b), 1
     y = empty_cl(b, c, p, a, xac.device, xac.dtype)
-    _lib.check(lib.epn_norm_act_pair_frozen_fwd(_cl_ptr(xac), _cl_ptr(xbc), b, rows, c, ctypes.byref(sa), ctypes.byref(sb),
-                                                float(slope), _cl_ptr(y), int(xac.dtype == torch.bfloat16),
-                                                _lib.stream_of(xac)), "norm_act_pair_frozen_fwd")
+    _pair_call("frozen_fwd", (_cl_ptr(xac), _cl_ptr(xbc), b, p * a, c, ctypes.byref(sa), ctypes.byref(sb), float(slope),
+                              _cl_ptr(y), int(xac.dtype == torch.bfloat16)), _lib.stream_of(xac))
     return y
 
 
@@ -1850,24 +1827,14 @@ def _norm_to_spectral_eval(f, norm, slope, basis, part=None):
     """ToSpectral(leaky_relu(norm(f))) in eval() mode (forward only), the norm applied as the basis change loads its rows: frozen
     statistics (epn_so3_basis_norm_frozen_*), or NormToSpectralFn's forward on the batch's statistics without the running
     update.  f: channels-last [b,c,p,a]."""
-    import torch.nn as nn
     kind = _eval_kind(norm)
     _forward_only("intra_so3conv(pre_eval=True)", f, *norm.parameters())
     if kind == "batch":
+        gamma, beta, instance, eps = _norm_params(norm)
         with torch.no_grad():
-            return NormToSpectralFn.apply(f, getattr(norm, "weight", None), getattr(norm, "bias", None), None,
-                                          isinstance(norm, nn.InstanceNorm2d), norm.eps, slope, basis, part)[0]
-    lib = _lib.get_lib()
-    b, c, p, na = f.shape
+            return NormToSpectralFn.apply(f, gamma, beta, None, instance, eps, slope, basis, part)[0]
     stats = _frozen_stats(norm, None)
-    g, bt = _affine(norm)
-    y = torch.empty(na * b * p * c, dtype=f.dtype, device=f.device)
-    _run(("so3_basis", ("so3_basis", b * p, c), 2.0 * b * p * na * na * c, f.device), "so3_basis_norm_frozen",
-         _entry(lib, "so3_basis_norm_frozen", f.dtype), _cl_ptr(f), _lib.dev_ptr(basis.Ut, "M"),
-         _lib.dev_ptr(basis.blocks, "blocks", torch.int32), ctypes.c_longlong(b * p), na, c, 1, ctypes.c_void_p(y.data_ptr()),
-         _lib.dev_ptr(stats, "stats"), _lib.dev_ptr(g, "gamma"), _lib.dev_ptr(bt, "beta"), float(norm.eps), float(slope),
-         _lib.stream_of(f))
-    return y
+    return _norm_to_spectral(f, basis, "so3_basis_norm_frozen", (_lib.dev_ptr(stats, "stats"),), *_affine(norm), norm.eps, slope)
 
 
 def deterministic_bwd(dtype):

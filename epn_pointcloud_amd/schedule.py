@@ -204,23 +204,17 @@ class FusedSeparableBlock(SeparableBlock):
         conv = self.inter_conv.conv
         # x.feats feeds the inter convolution AND the skip branch: the convolution hands back the tensor for the second use
         # and folds that branch's gradient into its own data gradient (ops.InterSO3ConvSplitFn; EPN_SHARE_INPUT_GRAD=0: off)
-        conv.share_input_grad = True
         # two-piece fp16 GEMMs: max|x| once for both consumers of the block input (the grouped features' bound K max|x| and
         # the skip convolution; a strided block's gathered rows are a subset: the same scalar bounds them)
         x_amax = None
         if x.feats.is_cuda and ops.gemm.f16x2_on(x.feats) and x.feats.shape[1] >= 16:
             x_amax = ops.gemm.absmax_cached(ops.to_cl(x.feats))
-        try:
-            inter_idx, inter_w, sample_idx, y = conv(x, inter_idx, inter_w)
-        finally:
-            conv.share_input_grad = False
-        skip = conv.__dict__.pop("_shared_input", None)
+        inter_idx, inter_w, sample_idx, y, (skip, y_part) = conv(x, inter_idx, inter_w, share_input=True)
         if skip is None:
             skip = x.feats
         # per-channel statistics of the two GEMM outputs that a norm follows (inter convolution, skip convolution) come from
         # the GEMMs' epilogues (block partials; EPN_EPILOGUE_STATS=0: separate passes over the tensors)
         epi = ab("EPN_EPILOGUE_STATS") == "1"
-        y_part = conv.__dict__.pop("_out_stats", None)
         y_part = y_part if epi else None
 
         pair = ab("EPN_NORM_PAIR") == "1" and not drop    # skip norm folded into the block's final pass
@@ -254,14 +248,9 @@ class FusedSeparableBlock(SeparableBlock):
         if not drop and ab("EPN_NORM_ON_LOAD") == "1" and self.intra_conv.conv.takes_spectral_form(y.feats.is_cuda):
             # norm + leaky_relu of the inter convolution applied as the intra convolution's basis change loads its
             # rows: the normalised tensor is never written
-            iconv = self.intra_conv.conv
-            iconv.want_out_stats = epi and pair
-            try:
-                z = iconv(zptk.SphericalPointCloud(y.xyz, y.feats, y.anchors), pre_norm=self.inter_conv.norm, pre_part=y_part,
-                          pre_eval=ev)
-            finally:
-                iconv.want_out_stats = False
-            z_part = iconv.__dict__.pop("_out_stats", None)
+            z = self.intra_conv.conv(zptk.SphericalPointCloud(y.xyz, y.feats, y.anchors), pre_norm=self.inter_conv.norm,
+                                     pre_part=y_part, pre_eval=ev, out_stats=epi and pair)
+            z, z_part = z if epi and pair else (z, None)
         else:
             feat = ops.norm_act_eval(y.feats, self.inter_conv.norm) if ev else ops.norm_act(y.feats, self.inter_conv.norm, dropout=drop)
             z = self.intra_conv.conv(zptk.SphericalPointCloud(y.xyz, feat, y.anchors))

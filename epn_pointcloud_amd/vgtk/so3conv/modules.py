@@ -80,7 +80,10 @@ class InterSO3Conv(nn.Module):
     """[b,c1,p1,a] -> [b,c2,p2,a]: convolution over the K spatial neighbours under every anchor rotation
     (modules.py:125-174).  forward(x, inter_idx=None, inter_w=None) ->
     (inter_idx, inter_w, sample_idx, SphericalPointCloud).  `inter_w` is returned as a lazy
-    ops.InterGeometry (call .dense() for the reference tensor); a dense tensor is accepted on input."""
+    ops.InterGeometry (call .dense() for the reference tensor); a dense tensor is accepted on input.
+    share_input=True (extension, for a block whose skip branch reads x.feats too): a fifth element (shared_input, out_stats)
+    -- x.feats for the caller's other use and the epilogue partials of the output's statistics, as ops.inter_so3conv
+    returns them; (None, None) when the convolution did not read x.feats itself (pooling)."""
 
     def __init__(self, dim_in, dim_out, kernel_size, stride, radius, sigma, n_neighbor,
                  lazy_sample=True, pooling=None, kanchor=60):
@@ -101,7 +104,7 @@ class InterSO3Conv(nn.Module):
         self.register_buffer('kernels', torch.from_numpy(np.ascontiguousarray(kernels)))
         self.feat_dtype = None     # output feature dtype; None = the input's (set by schedule.set_feature_dtype)
 
-    def forward(self, x, inter_idx=None, inter_w=None):
+    def forward(self, x, inter_idx=None, inter_w=None, share_input=False):
         xyz, feats = x.xyz, x.feats
         stride = self.stride
         if self.pooling is not None and stride > 1 and feats.shape[1] > 1:
@@ -128,13 +131,13 @@ class InterSO3Conv(nn.Module):
                 handle = inter_w
             else:
                 handle = ops.DenseInterWeights(inter_idx.int().contiguous(), inter_w, xyz.shape[2])
-        if getattr(self, "share_input_grad", False) and feats is x.feats:
-            # (set by a block whose skip branch reads x.feats too: see ops.InterSO3ConvSplitFn.forward)
-            out, self._shared_input, self._out_stats = ops.inter_so3conv(feats, self.basic_conv.W, handle, self.feat_dtype,
-                                                                         share_input=True)
+        shared = (None, None)
+        if share_input and feats is x.feats:        # (blurred features: nothing of x.feats to share)
+            out, *shared = ops.inter_so3conv(feats, self.basic_conv.W, handle, self.feat_dtype, share_input=True)
         else:
             out = ops.inter_so3conv(feats, self.basic_conv.W, handle, self.feat_dtype)
-        return inter_idx, inter_w, sample_idx, SphericalPointCloud(new_xyz, out, self.anchors)
+        ret = inter_idx, inter_w, sample_idx, SphericalPointCloud(new_xyz, out, self.anchors)
+        return ret + (tuple(shared),) if share_input else ret
 
 
 class IntraSO3Conv(nn.Module):
@@ -161,18 +164,17 @@ class IntraSO3Conv(nn.Module):
             self._idx32_cache, self._idx32_key = src.int().contiguous(), key
         return self._idx32_cache
 
-    def forward(self, x, pre_norm=None, pre_part=None, pre_eval=False):
+    def forward(self, x, pre_norm=None, pre_part=None, pre_eval=False, out_stats=False):
         """pre_norm (extension, used by schedule.FusedSeparableBlock): the norm module whose leaky_relu(norm(x.feats)) is the
         input -- folded into the convolution's basis change when it takes the block-diagonal form; pre_part: partial
         per-channel statistics of x.feats from the epilogue of the GEMM that produced it; pre_eval: the norm as it computes in
-        eval() mode (forward only, ops.norm_act_eval)."""
-        if getattr(self, "want_out_stats", False):       # set by a block whose norm follows: see ops.intra_so3conv
-            feats, self._out_stats = ops.intra_so3conv(x.feats, self.basic_conv.W, self._idx32(), pre_norm=pre_norm,
-                                                       pre_part=pre_part, out_stats=True, pre_eval=pre_eval)
-        else:
-            feats = ops.intra_so3conv(x.feats, self.basic_conv.W, self._idx32(), pre_norm=pre_norm, pre_part=pre_part,
-                                      pre_eval=pre_eval)
-        return SphericalPointCloud(x.xyz, feats, self.anchors)
+        eval() mode (forward only, ops.norm_act_eval); out_stats (for a block whose norm follows): return (cloud, part), part
+        as ops.intra_so3conv(..., out_stats=True) returns it."""
+        out = ops.intra_so3conv(x.feats, self.basic_conv.W, self._idx32(), pre_norm=pre_norm, pre_part=pre_part,
+                                out_stats=out_stats, pre_eval=pre_eval)
+        if out_stats:
+            return SphericalPointCloud(x.xyz, out[0], self.anchors), out[1]
+        return SphericalPointCloud(x.xyz, out, self.anchors)
 
     def takes_spectral_form(self, is_cuda=True):
         return ops.intra_takes_spectral(self.dim_in, self.dim_out, self._idx32(), is_cuda)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Which form did every layer take?  One eager training step (forward, backward, optimiser) of each configuration below
-under ops.profile_begin() / profile_end(), written as one text file per configuration: a line `kind key flops kernel` per
+"""Which form did every layer take?  One eager step (forward, backward, optimiser; or the forward alone) of each configuration
+below under ops.profile_begin() / profile_end(), written as one text file per configuration: a line `kind key flops kernel` per
 recorded launch, in launch order.  Two trees that select the same forms, launch the same kernels in the same order and
 report the same flop counts produce identical files:
 
@@ -18,7 +18,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# name -> (model, dtype, forward_only, environment)
+# name -> (model, dtype, forward_only, environment[, {"dropout_rate": rate} | {"eval": True}])
 CONFIGS = {}
 for _m in ("f16x2", "split", "native"):
     CONFIGS[f"cls_f32_gemm_{_m}"] = ("cls", "f32", False, {"EPN_GEMM_FP32": _m})
@@ -34,25 +34,30 @@ for _m in ("cloud", "split", "onchip", "fused"):
 CONFIGS["cls_f32_no_shared_grad"] = ("cls", "f32", False, {"EPN_AB": "1", "EPN_SHARE_INPUT_GRAD": "0"})
 CONFIGS["cls_f32_forward"] = ("cls", "f32", True, {})
 CONFIGS["reg_bf16_forward"] = ("reg", "bf16", True, {})
+CONFIGS["cls_f32_dropout"] = ("cls", "f32", False, {}, {"dropout_rate": 0.2})
+CONFIGS["cls_f32_eval"] = ("cls", "f32", True, {}, {"eval": True})              # eval() under no_grad: the forward-only glue
+CONFIGS["reg_bf16_eval"] = ("reg", "bf16", True, {}, {"eval": True})
 
 
 def run_one(name, out, batch):
     import torch
     sys.path.insert(0, ROOT)
     from epn_pointcloud_amd import models as M, ops, schedule as S
-    model_name, dtype, forward_only, _env = CONFIGS[name]
+    model_name, dtype, forward_only, _env, *extra = CONFIGS[name]
+    extra = extra[0] if extra else {}
+    drop = extra.get("dropout_rate", 0.0)
     dev = torch.device("cuda", 0)
     points = 2048 if model_name == "inv" else 1024
     batch = batch or (32 if model_name == "cls" else 64)
     layers = {"cls": S.cls_so3net_schedule, "reg": S.reg_so3net_schedule, "inv": S.inv_so3net_schedule}[model_name](points)
     torch.manual_seed(2913)
     if model_name == "cls":
-        model = M.ClsSO3ConvModel(layers, out_mlps=(256,), pooling="attention")
+        model = M.ClsSO3ConvModel(layers, out_mlps=(256,), pooling="attention", dropout_rate=drop)
     elif model_name == "reg":
-        model = M.RegSO3ConvModel(layers)
+        model = M.RegSO3ConvModel(layers, dropout_rate=drop)
     else:
-        model = M.InvSO3ConvModel(layers)
-    model = S.set_feature_dtype(model.to(dev).train(), torch.float32 if dtype == "f32" else torch.bfloat16)
+        model = M.InvSO3ConvModel(layers, dropout_rate=drop)
+    model = S.set_feature_dtype(model.to(dev).train(not extra.get("eval")), torch.float32 if dtype == "f32" else torch.bfloat16)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     pts = S.synthetic_clouds(batch, points, dev, seed=2913, scale=0.4 if model_name == "inv" else 1.0)
     labels = torch.arange(batch, device=dev) % 40
