@@ -3,11 +3,12 @@
 // channels (one 16-byte access per row) and walks rows with a fixed stride, so all global accesses are full-width
 // and coalesced and the per-channel reductions stay in registers until one LDS hop + one atomic per block.
 #include "conv_internal.h"
+#include "philox.h"
 
 namespace epn {
 namespace {
 
-constexpr int GT = 256;   // threads per block
+constexpr int GT = 256;  // threads per block
 
 // Activation tensors (x, dy, residual, y / dx) are float or __bf16 (template parameter T of the streaming kernels);
 // statistics, affine parameters and all arithmetic are fp32.
@@ -239,20 +240,8 @@ struct DropArgs {
     float scale;                       // 1 / (1 - rate)
 };
 
-struct u32x4 { unsigned w[4]; };
-__device__ __forceinline__ u32x4 philox4x32_10(unsigned long long ctr_lo, unsigned long long ctr_hi, unsigned long long key) {
-    unsigned c0 = (unsigned)ctr_lo, c1 = (unsigned)(ctr_lo >> 32), c2 = (unsigned)ctr_hi, c3 = (unsigned)(ctr_hi >> 32);
-    unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1;
-        c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return u32x4{{c0, c1, c2, c3}};
-}
+using philox::u32x4;              // philox.h: the generator is shared with patch_extract.hip
+using philox::philox4x32_10;
 
 // (seed, call) as a kernel holds them: read once through DropArgs::state (DROP), nothing otherwise
 template <bool DROP>

@@ -216,6 +216,44 @@ class InvSO3ConvModel(_SO3ConvModel):
     def forward(self, x):
         return self.outblock(self.features(x))
 
+    search_radius = None        # build_inv records the configuration's patch radius and size here: plain attributes, not
+    input_num = None            # buffers or parameters (the state_dict is the reference's, key for key)
+
+    def describe(self, pc, keypoints, *, radius=None, batch=64, seed=0):
+        """(pc f[n,3], keypoints f[k,3] or integer rows [k]) -> (descriptors f32 [k, c_out], valid bool [k]): the
+        descriptors of a fragment's keypoints.  The patches are extracted once on the device (vgtk.pc.radius_patches:
+        radius `radius` or the model's search_radius, input_num points each) and go through forward() in batches of `batch`
+        under torch.no_grad(), in the model's current mode, which must be eval(): dropout draws a mask per call.  Rows whose
+        ball holds at most one point do not go through the network: their descriptor is zero and valid is False.  The
+        last, partial batch is padded with zero patches whose rows are dropped."""
+        from .vgtk import pc as pctk
+        if self.training:
+            raise RuntimeError("describe() needs the model in eval() mode: call model.eval() first")
+        radius = self.search_radius if radius is None else radius
+        if radius is None or self.input_num is None:
+            raise ValueError("describe() needs the patch radius and size: build the model with build_inv, or set "
+                             "search_radius / input_num")
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f"batch must be >= 1, got {batch}")
+        with torch.no_grad():
+            patches, _, counts = pctk.radius_patches(pc, keypoints, radius, self.input_num, seed=seed)
+            valid = counts > 1
+            rows = torch.nonzero(valid).flatten()
+            desc = None
+            for r0 in range(0, rows.numel(), batch):
+                sel = rows[r0:r0 + batch]
+                x = patches.index_select(0, sel)
+                if x.shape[0] < batch:
+                    x = torch.cat((x, x.new_zeros(batch - x.shape[0], *x.shape[1:])))
+                d = self.forward(x)[0][:sel.numel()].float()
+                if desc is None:
+                    desc = d.new_zeros(valid.numel(), d.shape[1])
+                desc.index_copy_(0, sel, d)
+            if desc is None:                        # no valid row: the head's width without running it
+                desc = patches.new_zeros(valid.numel(), self.outblock.pointnet.embed.weight.shape[0])
+        return desc, valid
+
 
 class RegSO3ConvModel(_SO3ConvModel):
     """forward(x [b, 2, n, 3]) -> (confidence [b, na, na], rotations [b, 4 | 6, na, na]); the two clouds of a pair go
@@ -252,4 +290,6 @@ def build_reg(input_num=1024, width_div=1, **kw):
 def build_inv(input_num=2048, search_radius=0.4, width_div=1, **kw):
     """inv_so3net_pn.build_model defaults (mlps [[32,32],[64,64],[128,128],[128,128]], out_mlps [128,64])."""
     layers = S.scaled(S.inv_so3net_schedule(input_num, search_radius), width_div)
-    return InvSO3ConvModel(layers, out_mlps=tuple(max(c // width_div, 1) for c in (128, 64)), **kw)
+    model = InvSO3ConvModel(layers, out_mlps=tuple(max(c // width_div, 1) for c in (128, 64)), **kw)
+    model.search_radius, model.input_num = float(search_radius), int(input_num)      # what describe() extracts patches with
+    return model

@@ -44,6 +44,29 @@ def furthest_point_sampling(source_xyz, m):
     return idx
 
 
+def radius_patches(pc, kpts, radius, n_sample, seed=0, kpt_row0=0, key_bits=32, center=False, scale=1.0):
+    """(pc f[n,3], kpts f[k,3], float radius, int n_sample) -> (idx int32 [k,n_sample], counts int32 [k],
+    patches f[k,n_sample,3]): the points of one fragment within `radius` of every keypoint, resampled to n_sample
+    (epn_radius_patches_f32, include/epn_so3conv.h; no counterpart among the reference's extensions -- it replaces the
+    host KD-tree path of match_3dmatch.py:154-177 and vgtk/pc/sample.py:16-36).  kpt_row0 is the global row of kpts[0]."""
+    lib = _lib.get_lib()
+    _lib.same_device(pc, kpts)
+    p, q = _lib.dev_ptr(pc, "pc"), _lib.dev_ptr(kpts, "kpts")
+    if pc.dim() != 2 or pc.shape[1] != 3 or kpts.dim() != 2 or kpts.shape[1] != 3:
+        raise ValueError(f"pc must be [n,3] and kpts [k,3], got {tuple(pc.shape)} and {tuple(kpts.shape)}")
+    n, k, ns = pc.shape[0], kpts.shape[0], int(n_sample)
+    if not 1 <= ns <= 8192:
+        raise ValueError(f"n_sample must be in 1..8192, got {ns}")
+    idx = torch.empty((k, ns), dtype=torch.int32, device=pc.device)
+    counts = torch.empty((k,), dtype=torch.int32, device=pc.device)
+    patches = torch.empty((k, ns, 3), dtype=torch.float32, device=pc.device)
+    _lib.check(lib.epn_radius_patches_f32(p, n, q, k, int(kpt_row0), float(radius), ns, int(seed) & (2 ** 64 - 1),
+                                          int(key_bits), int(bool(center)), float(scale),
+                                          _lib.dev_ptr(idx, "idx", torch.int32), _lib.dev_ptr(counts, "counts", torch.int32),
+                                          _lib.dev_ptr(patches, "patches"), _lib.stream_of(pc)), "radius_patches")
+    return idx, counts, patches
+
+
 def initial_anchor_query(centers, xyz, kernel_points, radius, sigma):
     """(centers f[b,3,nc], xyz f[m,3], kernel_points f[ks,na,3], radius, sigma) ->
     [anchor_weights f[b,ks,nc,na], anchor_ctn f[b,ks,nc,na]]  (grouping_cuda.cpp:138-158; KernelPropagation).  float32 or

@@ -98,6 +98,35 @@ int epn_gather_fwd_f64(const double *points, const int32_t *idx, int b, int c, i
 int epn_gather_bwd_f64(const double *grad_out, const int32_t *idx, int b, int c, int n, int m, double *grad_points,
                        epn_stream_t stream);
 
+/* Patch extraction around keypoints: every point of ONE fragment within `radius` of a keypoint, resampled to n_sample
+ * points.  Replaces the host path of the reference's 3DMatch loader -- scipy KDTree + query_ball_point per keypoint
+ * (SPConvNets/datasets/match_3dmatch.py:154-177), then np.random.choice to input_num points
+ * (vgtk/vgtk/pc/sample.py:16-36) -- whose selection is random and unordered; this is the library's own deterministic form
+ * of the same semantics.
+ *   pc f32[n,3] (row-major), kpts f32[k,3] -> idx i32[k,n_sample], counts i32[k], patches f32[k,n_sample,3].
+ * For keypoint row q, with global row Q = kpt_row0 + q (a caller that splits its keypoints over several calls gets the
+ * same rows):
+ *   in-radius set   S = { i : d2(i) <= r2 }, in individually rounded fp32 (no fma): dx = p.x - q.x (dy, dz alike),
+ *                   d2 = (dx*dx + dy*dy) + dz*dz, r2 = radius*radius; the comparison is inclusive, like
+ *                   query_ball_point.  counts[q] = |S|, not clamped.
+ *   key             key(i) = word0(Philox4x32-10(ctr_lo = i, ctr_hi = Q, key = seed)) >> (32 - key_bits)  -- the generator
+ *                   of the dropout masks below; key_bits (1..32, production value 32) keeps only the top bits, so that a
+ *                   test can force ties.
+ *   count <= 1      idx row all -1, patch row all zeros (the reference returns a zero patch for len(indices) <= 1).
+ *   count >= n_sample   the n_sample members of S smallest in (key, i) lexicographic order, written in ascending i: a
+ *                   uniformly random subset without replacement that does not depend on how the work is scheduled.
+ *   1 < count < n_sample   slots 0..count-1 hold S in ascending i; slot j >= count repeats slot
+ *                   word1(Philox4x32-10(ctr_lo = j, ctr_hi = Q, key = seed)) mod count: a draw with replacement, with a
+ *                   modulo bias of about count / 2^32.
+ *   patches         (pc[idx] - center * kpt) * scale, center 0 or 1; the subtraction is rounded first, then the multiply.
+ *                   With center = 0 and scale = 1 the values are bit copies of the fragment's.
+ * 1 <= n, 0 <= k, 1 <= n_sample <= 8192, 1 <= key_bits <= 32, radius finite and > 0, center 0 or 1, no NULL pointer when
+ * k > 0: EPN_EINVAL otherwise, decided before any HIP runtime call.  k == 0 succeeds and launches nothing.  One workgroup per
+ * keypoint, no workspace, no global atomics: the result is bitwise repeatable. */
+int epn_radius_patches_f32(const float *pc, int n, const float *kpts, int k, int64_t kpt_row0, float radius, int n_sample,
+                           uint64_t seed, int key_bits, int center, float scale, int32_t *idx, int32_t *counts,
+                           float *patches, epn_stream_t stream);
+
 /* ------------------------------------------------------------------ InterSO3Conv ------------ */
 
 /* Geometry + shapes of one inter convolution (vgtk/vgtk/so3conv/functional.py:118-178).
