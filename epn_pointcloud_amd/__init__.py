@@ -5,6 +5,7 @@ Holds only what the path needs:
   _lib.py    ctypes binding on torch device tensors (no CPU / eager fallback)
   vgtk/      host-side mirror of the reference's `vgtk` operator / nn.Module API for this path
   ops.py     autograd Functions over the C ABI (channels-last feature tensors)
+  matching.py  descriptor matching and the 3DMatch inlier ratio / recall on the device (after models.describe)
 
 `install_vgtk_alias()` registers the mirror under the reference's import names (`vgtk`,
 `vgtk.spconv`, `vgtk.so3conv`, `vgtk.cuda.grouping`, ...) so SPConvNets-style code imports unchanged.
@@ -22,3 +23,15 @@ def install_vgtk_alias():
         if name == prefix or name.startswith(prefix + "."):
             sys.modules["vgtk" + name[len(prefix):]] = mod
     return _v
+
+
+_MATCHING = ("match_descriptors", "evaluate_fragment_pair", "evaluate_scene")
+
+
+def __getattr__(name):
+    """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` (matching.py), resolved on
+    first use so that importing the package -- the build recipe does -- still needs no torch."""
+    if name in _MATCHING:
+        from . import matching
+        return getattr(matching, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -57,6 +57,7 @@ EXPORTS = [
     "epn_bn_frozen_stats_f32", "epn_norm_act_frozen_fwd_f32", "epn_norm_act_frozen_fwd_bf16", "epn_norm_act_pair_frozen_fwd",
     "epn_so3_basis_norm_frozen_f32", "epn_so3_basis_norm_frozen_split_f32", "epn_so3_basis_norm_frozen_bf16",
     "epn_radius_patches_f32",
+    "epn_nn_match_workspace_bytes", "epn_nn_match_f32", "epn_match_inliers_f64",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -310,6 +311,13 @@ def get_lib():
         getattr(lib, _n).argtypes = [_vp, _vp, _vp, _ll, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _vp]
     lib.epn_radius_patches_f32.argtypes = [_vp, _ci, _vp, _ci, ctypes.c_int64, _cf, _ci, ctypes.c_uint64, _ci, _ci, _cf, _vp, _vp,
                                            _vp, _vp]
+    # descriptor matching: every scene table twice (host copy for the checks, device copy for the kernels)
+    lib.epn_nn_match_workspace_bytes.argtypes = [ctypes.c_int64]
+    lib.epn_nn_match_workspace_bytes.restype = _sz
+    lib.epn_nn_match_f32.argtypes = [_vp, ctypes.c_int64, _ci, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]
+    lib.epn_match_inliers_f64.argtypes = [_vp, ctypes.c_int64, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          ctypes.c_double, _vp, _vp, _vp, _vp, _vp]
+    lib.epn_match_inliers_f64.restype = _ci
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

@@ -1,4 +1,7 @@
 """`vgtk.cuda.grouping` -- same function names/signatures as vgtk/vgtk/cuda/grouping_cuda.cpp:176-181."""
+import ctypes
+
+import numpy as np
 import torch
 
 from ... import _lib
@@ -65,6 +68,91 @@ def radius_patches(pc, kpts, radius, n_sample, seed=0, kpt_row0=0, key_bits=32, 
                                           _lib.dev_ptr(idx, "idx", torch.int32), _lib.dev_ptr(counts, "counts", torch.int32),
                                           _lib.dev_ptr(patches, "patches"), _lib.stream_of(pc)), "radius_patches")
     return idx, counts, patches
+
+
+def _scene_tables(frag_off, pairs, device):
+    """Host copies (contiguous numpy: what the library's argument checks read) and device copies (what its kernels read) of a
+    scene's tables, with out_off / tgt_off computed from them (include/epn_so3conv.h, "Scene tables")."""
+    fo = np.ascontiguousarray(np.asarray(frag_off, dtype=np.int64).reshape(-1))
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    if fo.size < 2:
+        raise ValueError("frag_off must hold F + 1 >= 2 offsets")
+    if pr.size and (pr.min() < 0 or pr.max() >= fo.size - 1):
+        raise ValueError(f"pairs must index fragments 0..{fo.size - 2}")
+    rows = np.diff(fo)
+    out_off = np.concatenate(([0], np.cumsum(rows[pr[:, 0]] + rows[pr[:, 1]]))).astype(np.int64)
+    tgt_off = np.concatenate(([0], np.cumsum(rows[pr[:, 1]]))).astype(np.int64)
+    host = dict(frag_off=fo, pairs=pr, out_off=out_off, tgt_off=tgt_off)
+    dev = {k: torch.from_numpy(v).to(device) for k, v in host.items()}
+    return host, dev
+
+
+def _table_args(host, dev, *names):
+    args = []
+    for n in names:
+        args += [ctypes.c_void_p(host[n].ctypes.data), ctypes.c_void_p(dev[n].data_ptr())]
+    return args
+
+
+def nn_match(feats, frag_off, pairs, valid=None):
+    """(feats f[R,C] device, frag_off i64[F+1] host, pairs i32[P,2] host, valid u8/bool [R] device or None) ->
+    (nn_idx int32 [out_off[P]], nn_d2 f[out_off[P]], out_off int64 [P+1] host tensor): the exact nearest valid row of the other
+    fragment in descriptor space, both directions of every pair in one launch; pair p's block holds its src rows, then its tgt
+    rows (epn_nn_match_f32, include/epn_so3conv.h; no counterpart among the reference's extensions -- it replaces the two
+    sklearn KDTrees of evaluation_3dmatch.py:77-84)."""
+    lib = _lib.get_lib()
+    f = _lib.dev_ptr(feats, "feats")
+    if feats.dim() != 2 or not 1 <= feats.shape[1] <= 128:
+        raise ValueError(f"feats must be [R,C] with 1 <= C <= 128, got {tuple(feats.shape)}")
+    if valid is not None:
+        _lib.same_device(feats, valid)
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        if valid.shape != (feats.shape[0],):
+            raise ValueError(f"valid must be [R] = [{feats.shape[0]}], got {tuple(valid.shape)}")
+    host, dev = _scene_tables(frag_off, pairs, feats.device)
+    n_out, P = int(host["out_off"][-1]), host["pairs"].shape[0]
+    nn_idx = torch.empty((n_out,), dtype=torch.int32, device=feats.device)
+    nn_d2 = torch.empty((n_out,), dtype=torch.float32, device=feats.device)
+    ws_bytes = int(lib.epn_nn_match_workspace_bytes(n_out))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=feats.device)
+    _lib.check(lib.epn_nn_match_f32(f, feats.shape[0], feats.shape[1], _lib.dev_ptr(valid, "valid", torch.uint8),
+                                    host["frag_off"].size - 1, *_table_args(host, dev, "frag_off"), P,
+                                    *_table_args(host, dev, "pairs", "out_off"), ctypes.c_void_p(ws.data_ptr()), ws_bytes,
+                                    _lib.dev_ptr(nn_idx, "nn_idx", torch.int32), _lib.dev_ptr(nn_d2, "nn_d2"),
+                                    _lib.stream_of(feats)), "nn_match")
+    return nn_idx, nn_d2, torch.from_numpy(host["out_off"])
+
+
+def match_inliers(kp_xyz, frag_off, pairs, nn_idx, gt, tau1):
+    """(kp_xyz f[R,3] device, frag_off, pairs as for nn_match, nn_idx from nn_match, gt f64 [P,4,4] taking tgt into src
+    coordinates, float tau1) -> (match_src int32 [tgt_off[P]], match_dist f64 [tgt_off[P]], n_match int32 [P],
+    n_inlier int32 [P], tgt_off int64 [P+1] host tensor): the mutual check tgt -> src -> tgt, the transformed distance in
+    fp64 and the counts per pair (epn_match_inliers_f64; replaces evaluation_3dmatch.py:86-100)."""
+    lib = _lib.get_lib()
+    _lib.same_device(kp_xyz, nn_idx)
+    k = _lib.dev_ptr(kp_xyz, "kp_xyz")
+    if kp_xyz.dim() != 2 or kp_xyz.shape[1] != 3:
+        raise ValueError(f"kp_xyz must be [R,3], got {tuple(kp_xyz.shape)}")
+    host, dev = _scene_tables(frag_off, pairs, kp_xyz.device)
+    n_out, n_tgt, P = int(host["out_off"][-1]), int(host["tgt_off"][-1]), host["pairs"].shape[0]
+    if nn_idx.shape != (n_out,):
+        raise ValueError(f"nn_idx must be [{n_out}] for these pairs, got {tuple(nn_idx.shape)}")
+    gt = torch.as_tensor(gt, dtype=torch.float64).reshape(-1, 4, 4).contiguous().to(kp_xyz.device)
+    if gt.shape[0] != P:
+        raise ValueError(f"gt must be [{P},4,4], got {tuple(gt.shape)}")
+    match_src = torch.empty((n_tgt,), dtype=torch.int32, device=kp_xyz.device)
+    match_dist = torch.empty((n_tgt,), dtype=torch.float64, device=kp_xyz.device)
+    n_match = torch.empty((P,), dtype=torch.int32, device=kp_xyz.device)
+    n_inlier = torch.empty((P,), dtype=torch.int32, device=kp_xyz.device)
+    _lib.check(lib.epn_match_inliers_f64(k, kp_xyz.shape[0], host["frag_off"].size - 1, *_table_args(host, dev, "frag_off"), P,
+                                         *_table_args(host, dev, "pairs", "out_off", "tgt_off"),
+                                         _lib.dev_ptr(nn_idx, "nn_idx", torch.int32), _lib.dev_ptr(gt, "gt", torch.float64),
+                                         float(tau1), _lib.dev_ptr(match_src, "match_src", torch.int32),
+                                         _lib.dev_ptr(match_dist, "match_dist", torch.float64),
+                                         _lib.dev_ptr(n_match, "n_match", torch.int32),
+                                         _lib.dev_ptr(n_inlier, "n_inlier", torch.int32), _lib.stream_of(kp_xyz)), "match_inliers")
+    return match_src, match_dist, n_match, n_inlier, torch.from_numpy(host["tgt_off"])
 
 
 def initial_anchor_query(centers, xyz, kernel_points, radius, sigma):

@@ -127,6 +127,55 @@ int epn_radius_patches_f32(const float *pc, int n, const float *kpts, int k, int
                            uint64_t seed, int key_bits, int center, float scale, int32_t *idx, int32_t *counts,
                            float *patches, epn_stream_t stream);
 
+/* Descriptor matching: for every fragment pair of a scene, the exact nearest neighbour in descriptor space in both
+ * directions, then the mutual check "tgt -> src -> tgt", the ground-truth transform and the inlier count.  Replaces the host
+ * block of the reference's evaluation (SPConvNets/datasets/evaluation_3dmatch.py:77-100: two sklearn KDTrees, the mutual
+ * mask, hom_transform, distances < tau1); this is the library's own deterministic statement of it.
+ *
+ * Scene tables (shared by the two entries below):
+ *   frag_off i64[F+1]  row offsets of the fragments in the concatenated arrays: frag_off[0] = 0, ascending (an empty
+ *                      fragment is allowed), frag_off[F] = R, fewer than 2^31 rows per fragment
+ *   pairs    i32[P,2]  (src fragment, tgt fragment), both in 0..F-1, src != tgt, P <= 32767
+ *   out_off  i64[P+1]  out_off[p] = sum over p' < p of n_src(p') + n_tgt(p'): pair p's block of the per-row outputs holds
+ *                      its n_src src rows first, then its n_tgt tgt rows
+ *   tgt_off  i64[P+1]  tgt_off[p] = sum over p' < p of n_tgt(p'): pair p's block of the per-tgt-row outputs
+ * Every table is passed twice: `*_host` is read by the argument checks (on the host, before any HIP runtime call), the
+ * unsuffixed pointer is the device copy the kernels read.  The caller computes out_off / tgt_off; the checks refuse tables
+ * that do not follow the formulas.  The two copies must hold the same values.
+ * Refusals: EPN_EINVAL for a size out of range, non-monotone offsets, a pair index out of range, src == tgt, or an offset
+ * table off its formula; EPN_ENULL for a required pointer that is NULL; EPN_EWORKSPACE for a workspace that is NULL or too
+ * small.  P == 0 (or no row at all) succeeds and launches nothing.
+ *
+ * epn_nn_match_f32 (replaces evaluation_3dmatch.py:77-84): feats f32[R,C], 1 <= C <= 128; valid u8[R] or NULL (all valid).
+ *   For query row i of one fragment of a pair and every row j of the other:
+ *     d2(i,j) = sum_c (a_ic - b_jc)^2, in fp32 FROM THE DIFFERENCES (never |a|^2 + |b|^2 - 2 a.b, which cancels twenty-fold
+ *     for unit descriptors with a neighbour at d2 ~ 0.05); the order and fusion of the C additions are not specified.
+ *     Row j is admissible iff it is valid and d2(i,j) is finite.
+ *   nn_idx i32[out_off[P]]: the fragment-local index of the admissible row with the smallest d2, ties to the lowest index;
+ *   nn_d2 f32[out_off[P]]: that d2.  An invalid query row, or one without an admissible candidate (a NaN row, an all-invalid
+ *   or empty fragment on the other side), gets nn_idx = -1 and nn_d2 = +inf.  An invalid row is never chosen.
+ *   Workspace: epn_nn_match_workspace_bytes(out_off[P]) bytes (host-only: 8 bytes per output row), 8-byte aligned.  The call
+ *   sets it to all-ones with a memset on `stream`, combines the target segments with one 64-bit atomicMin per query on the
+ *   key (bits(d2) << 32) | j, and unpacks it: the result does not depend on arrival order and is bitwise repeatable.
+ *
+ * epn_match_inliers_f64 (replaces evaluation_3dmatch.py:86-100): kp_xyz f32[R,3] keypoint coordinates in the row layout of
+ *   feats; nn_idx as written above; gt f64[P,4,4] (row-major) takes tgt coordinates into src coordinates; tau1 not NaN.
+ *   Tgt row j of pair p with s = nn_idx(tgt j) is mutual iff s >= 0 and nn_idx(src s) == j.  For a mutual row
+ *     dist(j) = | kp_src[s] - (R kp_tgt[j] + t) |  in fp64 (R, t: the upper 3 x 4 of gt[p]),  inlier iff dist < tau1.
+ *   match_src i32[tgt_off[P]] (s, or -1 if not mutual), match_dist f64[tgt_off[P]] (+inf if not mutual), n_match i32[P],
+ *   n_inlier i32[P].  One workgroup per pair; the counts are an integer reduction inside it (no atomics).
+ *   inlier_ratio = n_inlier / n_match is the host's (0 where n_match == 0; the reference divides by zero there). */
+size_t epn_nn_match_workspace_bytes(int64_t out_rows);
+int epn_nn_match_f32(const float *feats, int64_t R, int C, const uint8_t *valid, int F, const int64_t *frag_off_host,
+                     const int64_t *frag_off, int P, const int32_t *pairs_host, const int32_t *pairs,
+                     const int64_t *out_off_host, const int64_t *out_off, void *workspace, size_t workspace_bytes,
+                     int32_t *nn_idx, float *nn_d2, epn_stream_t stream);
+int epn_match_inliers_f64(const float *kp_xyz, int64_t R, int F, const int64_t *frag_off_host, const int64_t *frag_off, int P,
+                          const int32_t *pairs_host, const int32_t *pairs, const int64_t *out_off_host, const int64_t *out_off,
+                          const int64_t *tgt_off_host, const int64_t *tgt_off, const int32_t *nn_idx, const double *gt,
+                          double tau1, int32_t *match_src, double *match_dist, int32_t *n_match, int32_t *n_inlier,
+                          epn_stream_t stream);
+
 /* ------------------------------------------------------------------ InterSO3Conv ------------ */
 
 /* Geometry + shapes of one inter convolution (vgtk/vgtk/so3conv/functional.py:118-178).
