@@ -282,7 +282,12 @@ int epn_intra_so3conv_bwd_weight_f32(const float *feats_cl, const float *grad_ou
  * Backward: dsums f32[groups][c][2] = (sum dn, sum dn*xhat) with dn = dy * leaky'(.) * gamma, from
  * epn_norm_act_bwd_reduce_f32 (also writes dgamma / dbeta when given), then
  *   dx = rstd * (dn - mean(dn) - xhat * mean(dn * xhat))                               epn_norm_act_bwd_apply_f32 */
-size_t epn_norm_workspace_bytes(int groups, long long rows, int c);   /* scratch of the two reduction entry points */
+/* Scratch of the two reduction entry points: one (s1, s2) pair per block and channel,
+ *   bytes = groups * blocks * c * 8,   blocks = ceil(rows / rows_per_block),
+ *   rows_per_block = max(64, ceil(rows / ceil(1024 / groups)))
+ * (about 1024 blocks in total, never fewer than 64 rows each); 0 for a c the kernels do not take (c / 4 must be a power of two
+ * no greater than 256), groups > 65535, groups == 0 or rows == 0. */
+size_t epn_norm_workspace_bytes(int groups, long long rows, int c);
 /* BatchNorm2d's running statistics (training mode) from sums[c][2] of `count` values per channel, in one launch:
  * mean (+ conv_bias, the bias of the producing convolution when it was not added to x), unbiased variance,
  * num_batches_tracked += 1, running = running + momentum * (batch - running); momentum < 0 = None (cumulative average,
@@ -703,6 +708,8 @@ typedef struct epn_gemm_nt_problem {
 int epn_gemm_nt_f32(int nprob, const epn_gemm_nt_problem *probs, epn_stream_t stream);
 /* sums[g][c][2] = sum over the blocks_per_group consecutive 32-row blocks of group g of partials[block][c][2] (fixed
  * order: deterministic).  groups = 1 for BatchNorm2d, the number of clouds for InstanceNorm2d (rows per cloud % 32 == 0). */
+/* Workspace: 0 up to 2048 blocks per group (one kernel); above, the blocks are first summed 256 at a time into
+ * groups * ceil(blocks_per_group / 256) * c * 8 bytes. */
 size_t epn_stats_finish_workspace_bytes(int groups, long long blocks_per_group, int c);
 int epn_stats_finish(const float *partials, int groups, long long blocks_per_group, int c, float *sums, void *workspace,
                      size_t workspace_bytes, epn_stream_t stream);
