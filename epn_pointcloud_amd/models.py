@@ -219,13 +219,16 @@ class InvSO3ConvModel(_SO3ConvModel):
     search_radius = None        # build_inv records the configuration's patch radius and size here: plain attributes, not
     input_num = None            # buffers or parameters (the state_dict is the reference's, key for key)
 
-    def describe(self, pc, keypoints, *, radius=None, batch=64, seed=0):
+    def describe(self, pc, keypoints, *, radius=None, batch=64, seed=0, voxel_size=None):
         """(pc f[n,3], keypoints f[k,3] or integer rows [k]) -> (descriptors f32 [k, c_out], valid bool [k]): the
         descriptors of a fragment's keypoints.  The patches are extracted once on the device (vgtk.pc.radius_patches:
         radius `radius` or the model's search_radius, input_num points each) and go through forward() in batches of `batch`
         under torch.no_grad(), in the model's current mode, which must be eval(): dropout draws a mask per call.  Rows whose
         ball holds at most one point do not go through the network: their descriptor is zero and valid is False.  The
-        last, partial batch is padded with zero patches whose rows are dropped."""
+        last, partial batch is padded with zero patches whose rows are dropped.
+        voxel_size (a float, or "reference": vgtk.pc.reference_voxel_size(input_num)) downsamples the fragment to its voxel
+        centroids first (vgtk.pc.voxel_down_sample) and extracts the patches from those, as the reference's loaders do; integer
+        keypoints are rows of the ORIGINAL pc, resolved to coordinates before the downsampling.  None: the fragment as given."""
         from .vgtk import pc as pctk
         if self.training:
             raise RuntimeError("describe() needs the model in eval() mode: call model.eval() first")
@@ -237,6 +240,13 @@ class InvSO3ConvModel(_SO3ConvModel):
         if batch < 1:
             raise ValueError(f"batch must be >= 1, got {batch}")
         with torch.no_grad():
+            if voxel_size is not None:
+                if not keypoints.is_floating_point():
+                    if keypoints.dim() != 1:
+                        raise ValueError(f"integer keypoints must be [k] rows of pc, got {tuple(keypoints.shape)}")
+                    keypoints = pc.index_select(0, keypoints.long())
+                size = pctk.reference_voxel_size(self.input_num) if voxel_size == "reference" else float(voxel_size)
+                pc = pctk.voxel_down_sample(pc, size)[0]
             patches, _, counts = pctk.radius_patches(pc, keypoints, radius, self.input_num, seed=seed)
             valid = counts > 1
             rows = torch.nonzero(valid).flatten()

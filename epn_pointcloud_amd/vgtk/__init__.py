@@ -1,6 +1,7 @@
 """Mirror of the reference package `vgtk` (vgtk/vgtk/__init__.py:1-13), hot-path subset:
 functional, point3d, pc, spconv, so3conv, utils and the extension namespace `cuda`.
-Out of scope: app (trainer/logger), loss, transform, mesh, voxel."""
+Out of scope: app (trainer/logger), loss, transform, mesh, voxel (upstream's package of that name is
+empty; the voxel-grid downsampling the reference takes from open3d is pc.voxel_down_sample)."""
 from . import cuda  # noqa: F401
 from . import functional  # noqa: F401
 from . import point3d  # noqa: F401

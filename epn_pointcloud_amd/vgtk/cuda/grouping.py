@@ -70,6 +70,48 @@ def radius_patches(pc, kpts, radius, n_sample, seed=0, kpt_row0=0, key_bits=32, 
     return idx, counts, patches
 
 
+_VOXEL_FLAGS = ("bit 0: a coordinate exceeds 256 in magnitude",
+                "bit 1: a voxel index reaches 2^21 (the cloud's extent / voxel_size is too large)",
+                "bit 2: the hash table overflowed")
+
+
+def voxel_downsample(pc, voxel_size):
+    """(pc f[n,3], float voxel_size) -> (centroids f[M,3], counts int32 [M], first_idx int32 [M], point_voxel int32 [n]): one
+    centroid per occupied voxel of a fragment, voxels in ascending order of their lowest point index, point_voxel the row of
+    every point's voxel (-1 for a point with a non-finite coordinate) (epn_voxel_downsample_f32, include/epn_so3conv.h; no
+    counterpart among the reference's extensions -- it replaces open3d's voxel_down_sample of match_3dmatch.py:107-139).  The
+    status word is read back once; a range error raises ValueError naming its bit."""
+    lib = _lib.get_lib()
+    p = _lib.dev_ptr(pc, "pc")
+    if pc.dim() != 2 or pc.shape[1] != 3:
+        raise ValueError(f"pc must be [n,3], got {tuple(pc.shape)}")
+    vs = float(voxel_size)
+    if not (np.isfinite(vs) and vs > 0.0):
+        raise ValueError(f"voxel_size must be finite and > 0, got {voxel_size}")
+    n = pc.shape[0]
+    if n > 2 ** 22:
+        raise ValueError(f"voxel_downsample takes at most 2^22 points, got {n}")
+    i32 = dict(dtype=torch.int32, device=pc.device)
+    centroids = torch.empty((n, 3), dtype=torch.float32, device=pc.device)
+    counts, first_idx, point_voxel = torch.empty((n,), **i32), torch.empty((n,), **i32), torch.empty((n,), **i32)
+    if n == 0:
+        return centroids, counts, first_idx, point_voxel
+    status = torch.empty((2,), **i32)
+    ws_bytes = int(lib.epn_voxel_downsample_workspace_bytes(n))
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=pc.device)
+    _lib.check(lib.epn_voxel_downsample_f32(p, n, vs, _lib.dev_ptr(centroids, "centroids"),
+                                            _lib.dev_ptr(counts, "counts", torch.int32),
+                                            _lib.dev_ptr(first_idx, "first_idx", torch.int32),
+                                            _lib.dev_ptr(point_voxel, "point_voxel", torch.int32),
+                                            _lib.dev_ptr(status, "status", torch.int32), ctypes.c_void_p(ws.data_ptr()),
+                                            ws.numel() * 8, _lib.stream_of(pc)), "voxel_downsample")
+    m, flags = status.tolist()
+    if flags:
+        raise ValueError("voxel_downsample: status " + "; ".join(t for b, t in enumerate(_VOXEL_FLAGS) if flags >> b & 1)
+                         + f" (flags = {flags}, voxel_size = {vs})")
+    return centroids[:m], counts[:m], first_idx[:m], point_voxel
+
+
 def _scene_tables(frag_off, pairs, device):
     """Host copies (contiguous numpy: what the library's argument checks read) and device copies (what its kernels read) of a
     scene's tables, with out_off / tgt_off computed from them (include/epn_so3conv.h, "Scene tables")."""

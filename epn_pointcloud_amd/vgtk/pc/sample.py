@@ -42,6 +42,21 @@ def radius_patches(pc, keypoints, radius, n_sample, *, seed=0, center=False, sca
     return patches, idx, counts
 
 
+def voxel_down_sample(pc, voxel_size):
+    """[n,3] -> (centroids f[M,3], counts int32 [M], first_idx int32 [M], point_voxel int32 [n]): the centroid of every
+    occupied voxel of edge voxel_size, on the device.  What the reference does on the host with open3d before it searches a
+    fragment (pcd.voxel_down_sample, match_3dmatch.py:107-139), in the library's deterministic statement of it
+    (include/epn_so3conv.h: epn_voxel_downsample_f32): voxels in ascending order of their lowest point index, points with a
+    non-finite coordinate dropped (point_voxel -1), a cloud out of range raises ValueError."""
+    return cuda_nn.voxel_downsample(pc.contiguous(), voxel_size)
+
+
+def reference_voxel_size(input_num):
+    """The voxel size the reference's 3DMatch loaders downsample a fragment with before extracting patches of input_num
+    points (match_3dmatch.py:258, :371, :445)."""
+    return 0.03 if input_num < 1024 else 0.015
+
+
 def furthest_sample_index(pc, n_sample, lazy_sample):
     """sample.py:63-72: arange when nothing is dropped or lazy_sample, FPS kernel otherwise."""
     if pc.shape[2] == n_sample or lazy_sample:

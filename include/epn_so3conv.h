@@ -176,6 +176,37 @@ int epn_match_inliers_f64(const float *kp_xyz, int64_t R, int F, const int64_t *
                           double tau1, int32_t *match_src, double *match_dist, int32_t *n_match, int32_t *n_inlier,
                           epn_stream_t stream);
 
+/* Voxel-grid downsampling: one centroid per occupied voxel of ONE fragment.  The reference never searches the raw fragment:
+ * radius_ball_search_o3d (SPConvNets/datasets/match_3dmatch.py:107-139) calls open3d's pcd.voxel_down_sample(voxel_size)
+ * first (0.03 below 1024 input points, 0.015 from there: :258, :371, :445) and builds its KD-tree over the centroids.  This is
+ * open3d's VoxelDownSample made deterministic; it has not been run against open3d.
+ *   pc f32[n,3] (row-major), voxel_size (a double, as in open3d) -> centroids f32[M,3], counts i32[M], first_idx i32[M],
+ *   point_voxel i32[n], status i32[2] = {M, flags} on the device.  The caller allocates n rows for the per-voxel outputs.
+ *   dropped points  a point with any non-finite coordinate takes no part in anything below; its point_voxel entry is -1.
+ *   voxel index     lo = per-axis minimum over the kept points (an fp32 minimum: exact, independent of order).  In fp64:
+ *                   vmin = (double)lo - 0.5 * voxel_size,  ix = floor(((double)x - vmin) / voxel_size)  (iy, iz alike) --
+ *                   open3d's voxel_min_bound and floor(ref_coord).  key = ix << 42 | iy << 21 | iz.
+ *   range errors    flags bit 0: a kept |coordinate| > 256; bit 1: an index >= 2^21; (bit 2: the table overflowed, which the
+ *                   load factor below excludes).  With flags != 0 nothing else in the outputs is defined; nothing is
+ *                   dropped silently.
+ *   centroid        per coordinate fx = llrint((double)x * 2^32) (exact for |x| >= 2^-9), summed as 64-bit integers over the
+ *                   voxel's points (256 * 2^32 * 2^22 < 2^63), so the sum does not depend on order and is bitwise repeatable;
+ *                   centroid = (float)((double)sum / ((double)count * 2^32)).
+ *   output order    voxels in ascending order of their lowest member point index (open3d's order is its hash map's);
+ *                   first_idx holds that index, point_voxel the output row of each kept point's voxel.  The rows are ranked
+ *                   by a prefix sum over "first point of its voxel" flags in tiles of 256 points: per-tile counts, one
+ *                   workgroup that scans the counts 256 at a time, the write pass.
+ * Hash table (stated because tests construct collisions from it): open addressing in the caller's workspace, capacity the
+ * smallest power of two >= max(2n, 128), an empty slot's key all-ones (no valid key has bit 63 set), home slot
+ * (key * 0x9E3779B97F4A7C15) >> (64 - log2(capacity)) in 64-bit wrapping arithmetic, probed linearly with wrap-around.
+ * Workspace: epn_voxel_downsample_workspace_bytes(n) bytes (host-only), 8-byte aligned; initialised by the call itself.
+ * 0 <= n <= 2^22, voxel_size finite and > 0, no NULL pointer and a large enough workspace when n > 0: EPN_EINVAL otherwise,
+ * decided before any HIP runtime call.  n == 0 succeeds, launches nothing and leaves status untouched. */
+size_t epn_voxel_downsample_workspace_bytes(int64_t n);
+int epn_voxel_downsample_f32(const float *pc, int64_t n, double voxel_size, float *centroids, int32_t *counts,
+                             int32_t *first_idx, int32_t *point_voxel, int32_t *status, void *workspace,
+                             size_t workspace_bytes, epn_stream_t stream);
+
 /* ------------------------------------------------------------------ InterSO3Conv ------------ */
 
 /* Geometry + shapes of one inter convolution (vgtk/vgtk/so3conv/functional.py:118-178).
