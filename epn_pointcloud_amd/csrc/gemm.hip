@@ -355,7 +355,7 @@ int launch_nt_typed(GemmNtBatch &B, hipStream_t st) {
     for (int i = 0; i < B.nprob; ++i) {
         const GemmNtProb &p = B.p[i];
         if (p.M < 0 || p.N < 1 || p.K < 1 || (p.stats && p.M % 32)) return EPN_EINVAL;
-        if (!p.A || !p.Bt || !p.C) return EPN_ENULL;
+        if (!p.Bt || (p.M > 0 && (!p.A || !p.C))) return EPN_ENULL;     // (an empty problem has nothing to point at)
         if (p.K % (4 * E16) || p.lda % E16 || p.ldb % E16 || ((uintptr_t)p.A & 15) || ((uintptr_t)p.Bt & 15)) fast = false;
         if (p.K % (8 * E16)) half_k = true;      // K a multiple of 4 slots only: the short-K-step kernels
         maxn = p.N > maxn ? p.N : maxn;

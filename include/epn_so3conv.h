@@ -719,7 +719,8 @@ int epn_zp_intra_bwd_f32(const int32_t *anchor_neighbors, const float *anchor_we
  *                                           fp32 partials in `workspace`, summed in a fixed order: deterministic).
  * fp32: v_mfma_f32_32x32x2_f32, exact f32 (the split entry points below: the bf16 pipe at fp32 accuracy).  bf16: bf16 operands, fp32 accumulation; NT writes bf16 (or fp32 when
  * out_f32 != 0), TN always writes fp32.  Fast path: K % 32 == 0 (fp32) / 64 (bf16), 16-byte aligned rows; anything
- * else runs on a generic kernel.  C is fully overwritten. */
+ * else runs on a generic kernel.  C is fully overwritten.  An NT problem with M == 0 is empty: nothing is read or written for
+ * it, and its A and C may be NULL (Bt, N >= 1 and K >= 1 are still required); it may stand anywhere in a grouped call. */
 typedef struct epn_gemm_nt_problem {
     const void *A, *Bt;
     void *C;
