@@ -6,6 +6,7 @@ Holds only what the path needs:
   vgtk/      host-side mirror of the reference's `vgtk` operator / nn.Module API for this path
   ops.py     autograd Functions over the C ABI (channels-last feature tensors)
   matching.py  descriptor matching and the 3DMatch inlier ratio / recall on the device (after models.describe)
+  alignment.py  rotation decode, chordal mean and angular error on the device (after RegSO3ConvModel.forward)
 
 `install_vgtk_alias()` registers the mirror under the reference's import names (`vgtk`,
 `vgtk.spconv`, `vgtk.so3conv`, `vgtk.cuda.grouping`, ...) so SPConvNets-style code imports unchanged.
@@ -26,12 +27,17 @@ def install_vgtk_alias():
 
 
 _MATCHING = ("match_descriptors", "evaluate_fragment_pair", "evaluate_scene")
+_ALIGNMENT = ("decode_rotation", "evaluate_alignment")
 
 
 def __getattr__(name):
-    """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` (matching.py), resolved on
-    first use so that importing the package -- the build recipe does -- still needs no torch."""
+    """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` (matching.py) and
+    `.decode_rotation` / `.evaluate_alignment` (alignment.py), resolved on first use so that importing the package -- the
+    build recipe does -- still needs no torch."""
     if name in _MATCHING:
         from . import matching
         return getattr(matching, name)
+    if name in _ALIGNMENT:
+        from . import alignment
+        return getattr(alignment, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -59,6 +59,7 @@ EXPORTS = [
     "epn_radius_patches_f32",
     "epn_nn_match_workspace_bytes", "epn_nn_match_f32", "epn_match_inliers_f64",
     "epn_voxel_downsample_workspace_bytes", "epn_voxel_downsample_f32",
+    "epn_rotation_labels_f32", "epn_so3_mean_f32", "epn_rotation_decode_f32",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -322,6 +323,10 @@ def get_lib():
     lib.epn_voxel_downsample_workspace_bytes.argtypes = [ctypes.c_int64]
     lib.epn_voxel_downsample_workspace_bytes.restype = _sz
     lib.epn_voxel_downsample_f32.argtypes = [_vp, ctypes.c_int64, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+    # rotation estimation: (anchors, T, b, A, ...), (Rs, weights, b, N, ...), (wts, y, anchors, label, gt_T, b, A, nr, ...)
+    lib.epn_rotation_labels_f32.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp, _vp]
+    lib.epn_so3_mean_f32.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp, _vp]
+    lib.epn_rotation_decode_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

@@ -284,6 +284,35 @@ class RegSO3ConvModel(_SO3ConvModel):
         x1, x2 = torch.chunk(x.xyz, 2, dim=0)
         return self.outblock(f1, f2, x1, x2)
 
+    def estimate_rotation(self, src, tgt, *, batch=32):
+        """(src f32 [k,n,3], tgt f32 [k,n,3]) -> (R f32 [k,3,3], margin f32 [k], preds int32 [k,A], conf f32 [k,A]): the
+        rotation of every pair (R applied to tgt's shape gives src's, as in the reference's loader), the conditioning of the
+        mean it comes from (vgtk.functional.so3_mean) and, per source anchor, the chosen target anchor and its normalised
+        confidence.  The pairs go through forward() in batches of `batch` under torch.no_grad(), in the model's current mode,
+        which must be eval() as for describe(); the last, partial batch is padded with zero clouds whose rows are dropped.
+        Each batch is decoded on the device with the model's own anchors and the head's representation (alignment.py:
+        decode_rotation).  Everything is checked on the host before the first device call; k = 0 returns empty tensors
+        without a launch."""
+        from . import alignment
+        if self.training:
+            raise RuntimeError("estimate_rotation() needs the model in eval() mode: call model.eval() first")
+        batch = alignment.check_pairs(src, tgt, batch)
+        anchors = self.get_anchor()
+        A, nr = anchors.shape[0], self.outblock.out_channel
+        if not 1 <= A <= 64:
+            raise ValueError(f"estimate_rotation() decodes at most 64 anchors, the model has {A}")
+        if nr not in (4, 6):
+            raise ValueError(f"the head regresses {nr} values per anchor pair; the decode knows 4 (quat) and 6 (ortho6d)")
+        k = src.shape[0]
+        if k == 0:
+            return (src.new_zeros((0, 3, 3)), src.new_zeros((0,)), src.new_zeros((0, A), dtype=torch.int32),
+                    src.new_zeros((0, A)))
+        if not src.is_cuda:
+            raise RuntimeError("src must be a CUDA tensor")
+        with torch.no_grad():
+            d = alignment.batched_decode(self, src, tgt, batch)
+        return d.pred_R, d.margin, d.preds, d.conf
+
 
 def build_cls(input_num=1024, width_div=1, **kw):
     """cls_so3net_pn.build_model defaults (mlps [[64,64],[128,128],[256,256],[256]], out_mlps [256])."""

@@ -207,6 +207,52 @@ int epn_voxel_downsample_f32(const float *pc, int64_t n, double voxel_size, floa
                              int32_t *first_idx, int32_t *point_voxel, int32_t *status, void *workspace,
                              size_t workspace_bytes, epn_stream_t stream);
 
+/* Rotation estimation: what turns RegSO3ConvModel's head output into a rotation, the labels a training step needs and the
+ * angular error the reference reports.  All tensors are contiguous device memory, float or int32; anchors
+ * f32[A,3,3], 1 <= A <= 64.  Arithmetic is fp64 on the fp32 inputs and every output is rounded once to fp32.  One wave per
+ * pair, lane a owns source anchor a; sums over lanes are a fixed xor tree, so results are bitwise repeatable.  No workspace, no
+ * atomics, every loop bounded by A, N or a fixed sweep count.  A pair with non-finite inputs leaves its own rows unspecified
+ * (its preds still lie in 0..A-1) and touches nothing else.
+ * Refusals, decided before any HIP runtime call: EPN_EINVAL for b < 0, A outside 1..64, nr not 4 or 6, N < 1; then b == 0
+ * succeeds and launches nothing; then EPN_ENULL for a required pointer that is NULL.
+ *
+ * epn_rotation_labels_f32 (label_relative_rotation_np, vgtk/vgtk/functional/rotation.py:521-526, per pair on the device in
+ *   place of Dataloader_ModelNet40Alignment's per-sample numpy, SPConvNets/datasets/modelnet40.py:152): T f32[b,3,3] ->
+ *   R_target f32[b,A,3,3], label i32[b,A].  M(a,i) = A_a^T T A_i; label[a] = the i with the largest tr M(a,i), the lowest
+ *   such i on a tie (compared in fp64); R_target[a] = M(a, label[a]).
+ *
+ * epn_so3_mean_f32 (so3_mean, rotation.py:481-518, without torch.svd): Rs f32[b,N,3,3], weights f32[b,N] or NULL (all ones)
+ *   -> R f32[b,3,3], margin f32[b].  Ce = sum_n w_n Rs_n (lane l adds n = l, l + 64, ... in ascending order, then the tree).
+ *   R is the rotation that maximises tr(R^T Ce): U diag(1, 1, det(U V^T)) V^T of Ce's singular value decomposition,
+ *   Ce = U diag(s1 >= s2 >= s3) V^T.  margin = (s2 + det(U V^T) s3) / s1, the conditioning of that projection: R moves by at
+ *   most 2 |dCe| / (s1 margin) under a perturbation dCe, and is not unique at margin 0.  Ce exactly zero: R = I, margin = 0.
+ *   Method: tr(R(q)^T Ce) = q^T K q for the unit quaternion q of R, K the symmetric 4 x 4 matrix of Horn's closed form; its
+ *   eigenvalues are s1 + s2 + d s3 >= s1 - s2 - d s3 >= ..., so q is the top eigenvector (cyclic Jacobi, 12 sweeps),
+ *   s1 = (l1 + l2) / 2 and margin = (l1 - l2) / (l1 + l2).  R is always a rotation, whatever the margin.
+ *
+ * epn_rotation_decode_f32 (the alignment branch of MultiTaskDetectionLoss.forward without the loss, vgtk/vgtk/loss.py:140-172
+ *   and :210-218, with batched_select_anchor :77-92 and the two rotation maps rotation.py:379-417, :443-478):
+ *   wts f32[b,A,A] (target anchor, source anchor), y f32[b,nr,A,A], label i32[b,A] or NULL, gt_T f32[b,3,3] or NULL ->
+ *   pred_R f32[b,3,3], preds i32[b,A], conf f32[b,A], margin f32[b], pred_Rs f32[b,A,3,3] (or NULL: not wanted),
+ *   hits i32[b] (required and written iff label is given), err f32[b] (required and written iff gt_T is given).
+ *     preds[a]  = arg max over t of wts[t,a], fp32 comparison: t = 0 first, replaced on a strict >, so the lowest t wins a tie
+ *     c[a]      = wts[preds[a], a];  conf[a] = c[a] / (1e-6 + sum_a c[a])
+ *     R_a       = rotation map of y[:, preds[a], a].  nr = 4: q = (w,x,y,z) / max(|q|, 1e-8), rows
+ *                 (1-2yy-2zz, 2xy-2zw, 2xz+2yw), (2xy+2zw, 1-2xx-2zz, 2yz-2xw), (2xz-2yw, 2yz+2xw, 1-2xx-2yy).  nr = 6:
+ *                 x = n(y[0:3]), z = n(x cross y[3:6]), y' = z cross x, columns (x, y', z), n(v) = v / max(|v|, 1e-8).
+ *     pred_Rs[a] = A_a R_a A_preds[a]^T  (the einsum 'baij,bajk,balk->bail')
+ *     pred_R, margin = the projection above of sum_a conf[a] pred_Rs[a] (unrounded conf and pred_Rs)
+ *     hits      = the number of a with preds[a] == label[a]
+ *     err       = acos_safe(0.5 (sum_ij pred_R_ij gt_T_ij - 1)) on the unrounded pred_R, acos_safe(x) = acos(x) for
+ *                 |x| <= 1 - 1e-4 and acos(s (1 - 1e-4)) - s (|x| - 1 + 1e-4) acos(1 - 1e-4) / 1e-4, s = sign(x), beyond
+ *                 (vgtk/vgtk/spconv/functional.py:138-143). */
+int epn_rotation_labels_f32(const float *anchors, const float *T, int b, int A, float *R_target, int32_t *label,
+                            epn_stream_t stream);
+int epn_so3_mean_f32(const float *Rs, const float *weights, int b, int N, float *R, float *margin, epn_stream_t stream);
+int epn_rotation_decode_f32(const float *wts, const float *y, const float *anchors, const int32_t *label, const float *gt_T,
+                            int b, int A, int nr, float *pred_R, int32_t *preds, float *conf, float *margin, float *pred_Rs,
+                            int32_t *hits, float *err, epn_stream_t stream);
+
 /* ------------------------------------------------------------------ InterSO3Conv ------------ */
 
 /* Geometry + shapes of one inter convolution (vgtk/vgtk/so3conv/functional.py:118-178).
