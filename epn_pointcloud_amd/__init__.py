@@ -5,7 +5,7 @@ Holds only what the path needs:
   _lib.py    ctypes binding on torch device tensors (no CPU / eager fallback)
   vgtk/      host-side mirror of the reference's `vgtk` operator / nn.Module API for this path
   ops.py     autograd Functions over the C ABI (channels-last feature tensors)
-  matching.py  descriptor matching and the 3DMatch inlier ratio / recall on the device (after models.describe)
+  matching.py  descriptor matching, the 3DMatch inlier ratio / recall and pairwise registration on the device (after models.describe)
   alignment.py  rotation decode, chordal mean and angular error on the device (after RegSO3ConvModel.forward)
 
 `install_vgtk_alias()` registers the mirror under the reference's import names (`vgtk`,
@@ -26,12 +26,14 @@ def install_vgtk_alias():
     return _v
 
 
-_MATCHING = ("match_descriptors", "evaluate_fragment_pair", "evaluate_scene")
+_MATCHING = ("match_descriptors", "evaluate_fragment_pair", "evaluate_scene", "register_scene", "register_fragment_pair",
+             "registration_errors", "registration_recall", "RegistrationResult")
 _ALIGNMENT = ("decode_rotation", "evaluate_alignment")
 
 
 def __getattr__(name):
-    """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` (matching.py) and
+    """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` / `.register_scene` /
+    `.register_fragment_pair` / `.registration_errors` / `.registration_recall` (matching.py) and
     `.decode_rotation` / `.evaluate_alignment` (alignment.py), resolved on first use so that importing the package -- the
     build recipe does -- still needs no torch."""
     if name in _MATCHING:

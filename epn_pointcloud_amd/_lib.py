@@ -60,6 +60,7 @@ EXPORTS = [
     "epn_nn_match_workspace_bytes", "epn_nn_match_f32", "epn_match_inliers_f64",
     "epn_voxel_downsample_workspace_bytes", "epn_voxel_downsample_f32",
     "epn_rotation_labels_f32", "epn_so3_mean_f32", "epn_rotation_decode_f32",
+    "epn_ransac_register_workspace_bytes", "epn_ransac_register_f64",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -327,6 +328,14 @@ def get_lib():
     lib.epn_rotation_labels_f32.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp, _vp]
     lib.epn_so3_mean_f32.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp, _vp]
     lib.epn_rotation_decode_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    # pairwise registration: (kp_xyz, R, F, frag_off x2, P, pairs x2, tgt_off x2, match_src, tau, H, seed, pair0, min_margin,
+    # workspace, bytes, T, best_h, hyp_count, n_inlier, rmse, margin, stream)
+    lib.epn_ransac_register_workspace_bytes.argtypes = [ctypes.c_int64]
+    lib.epn_ransac_register_workspace_bytes.restype = _sz
+    lib.epn_ransac_register_f64.argtypes = [_vp, ctypes.c_int64, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _ci,
+                                            ctypes.c_uint64, ctypes.c_int64, ctypes.c_double, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp]
+    lib.epn_ransac_register_f64.restype = _ci
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

@@ -9,6 +9,10 @@ The file readers (.ply, keypoint lists, gt.log) stay with the caller.  Specifica
 
 Descriptors, keypoints and masks are device tensors (what describe() returns); the small per-pair results come back as numpy
 arrays, like the reference's.  A whole scene is one nearest-neighbour launch and one inlier launch.
+
+Without ground truth: `register_scene` / `register_fragment_pair` turn the mutual matches into the rigid transform between
+the fragments (RANSAC over three-point samples and a refit; epn_ransac_register_f64, DESIGN.md 3.1c, csrc/ransac_register.hip),
+and `registration_errors` / `registration_recall` score such transforms against known ones on the host.
 """
 import collections
 
@@ -23,6 +27,12 @@ SceneResult = collections.namedtuple("SceneResult", "n_inlier n_match inlier_rat
 SceneResult.__doc__ = """evaluate_scene's result: n_inlier, n_match int32 [P], inlier_ratio float64 [P] (0 where n_match is 0),
 matches (list of int32 [n_match, 2] arrays of (src row, tgt row) in ascending tgt row), distances (list of float64 [n_match]
 arrays) and recall, the reference's [(tau, 100 * mean(inlier_ratio > tau))]."""
+
+RegistrationResult = collections.namedtuple("RegistrationResult", "T n_match n_inlier rmse margin best_h")
+RegistrationResult.__doc__ = """register_scene's result, numpy arrays: T float64 [P,4,4] taking tgt coordinates into src coordinates
+(the identity for a failed pair), n_match int32 [P] mutual matches, n_inlier int32 [P] and rmse float64 [P] under T (0 and +inf
+for a failed pair), margin float64 [P], the conditioning of the refit's rotation (0: not unique), best_h int32 [P], the
+winning hypothesis (-1: the pair failed -- fewer than three matches, or no hypothesis with three inliers)."""
 
 
 def _concat(kps, feats, valids):
@@ -83,3 +93,48 @@ def match_descriptors(src_feats, tgt_feats, src_valid=None, tgt_valid=None):
     nn_idx, _, _ = grouping.nn_match(all_feats, frag_off, [[0, 1]], valid)
     match_src = grouping.match_inliers(all_kps, frag_off, [[0, 1]], nn_idx, np.eye(4)[None], 0.0)[0]
     return nn_idx[:ns], nn_idx[ns:], match_src >= 0
+
+
+def register_scene(kps, feats, valids, pairs, tau=0.05, hypotheses=4096, seed=0, min_margin=1e-2):
+    """(kps, feats, valids, pairs as for evaluate_scene; tau: the inlier distance; hypotheses per pair; seed of the draws;
+    min_margin: three-point samples whose fit is conditioned worse are rejected) -> RegistrationResult.  No ground truth: the
+    mutual matches come from the nearest-neighbour launch and the mutual check run the way match_descriptors runs it (identity
+    transforms, tau1 = 0), then the registration entry's three launches (compact, score, finish) cover every pair of the scene.
+    Pair p draws with the counter (p, seed): the same pair at the same position gives the same transform, bit for bit."""
+    all_kps, all_feats, valid, frag_off = _concat(kps, feats, valids)
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    P = pairs.shape[0]
+    nn_idx, _, _ = grouping.nn_match(all_feats, frag_off, pairs, valid)
+    match_src, _, n_match, _, tgt_off = grouping.match_inliers(all_kps, frag_off, pairs, nn_idx, np.tile(np.eye(4), (P, 1, 1)), 0.0)
+    T, best_h, _, n_inlier, rmse, margin = grouping.ransac_register(all_kps, frag_off, pairs, match_src, tgt_off, tau, hypotheses,
+                                                                    seed, min_margin)
+    host = lambda x: x.cpu().numpy()
+    return RegistrationResult(host(T), host(n_match), host(n_inlier), host(rmse), host(margin), host(best_h))
+
+
+def register_fragment_pair(src_kp, tgt_kp, src_feats, tgt_feats, tau=0.05, hypotheses=4096, seed=0, min_margin=1e-2,
+                           src_valid=None, tgt_valid=None):
+    """-> (T float64 [4,4] taking tgt into src coordinates, n_match int, n_inlier int, rmse float, margin float, best_h int):
+    register_scene on one pair (best_h == -1: the pair failed and T is the identity)."""
+    r = register_scene([src_kp, tgt_kp], [src_feats, tgt_feats], [src_valid, tgt_valid], [[0, 1]], tau=tau, hypotheses=hypotheses,
+                       seed=seed, min_margin=min_margin)
+    return r.T[0], int(r.n_match[0]), int(r.n_inlier[0]), float(r.rmse[0]), float(r.margin[0]), int(r.best_h[0])
+
+
+def registration_errors(T_est, T_gt):
+    """(T_est, T_gt float [P,4,4] or [4,4]) -> (rre_deg float64 [P], rte float64 [P]): the angle of R_gt^T R_est in degrees and
+    |t_est - t_gt|, numpy fp64 on the host."""
+    A = np.asarray(T_est, dtype=np.float64).reshape(-1, 4, 4)
+    B = np.asarray(T_gt, dtype=np.float64).reshape(-1, 4, 4)
+    if A.shape != B.shape:
+        raise ValueError(f"T_est and T_gt must have the same shape, got {A.shape} and {B.shape}")
+    tr = np.einsum("pij,pij->p", B[:, :3, :3], A[:, :3, :3])
+    rre = np.degrees(np.arccos(np.clip(0.5 * (tr - 1.0), -1.0, 1.0)))
+    return rre, np.linalg.norm(A[:, :3, 3] - B[:, :3, 3], axis=1)
+
+
+def registration_recall(T_est, T_gt, rre_deg=15.0, rte=0.3):
+    """The share of pairs with a rotation error below rre_deg degrees and a translation error below rte (the convention of the
+    learned-registration literature; both are parameters) -> float in [0, 1], 0.0 without pairs."""
+    r, t = registration_errors(T_est, T_gt)
+    return float(np.mean((r < rre_deg) & (t < rte))) if r.size else 0.0

@@ -197,6 +197,50 @@ def match_inliers(kp_xyz, frag_off, pairs, nn_idx, gt, tau1):
     return match_src, match_dist, n_match, n_inlier, torch.from_numpy(host["tgt_off"])
 
 
+def ransac_register(all_kps, frag_off, pairs, match_src, tgt_off, tau, hypotheses, seed, min_margin, pair0=0):
+    """(all_kps f[R,3] device, frag_off, pairs as for nn_match, match_src int32 [tgt_off[P]] and tgt_off from match_inliers,
+    float tau, int hypotheses per pair, int seed, float min_margin, int pair0 = the counter word of pairs[0]) ->
+    (T f64 [P,4,4], best_h int32 [P], hyp_count int32 [P,H], n_inlier int32 [P], rmse f64 [P], margin f64 [P]), device tensors:
+    the rigid transform tgt -> src of every pair by RANSAC over its mutual matches and one refit on the winner's inliers
+    (epn_ransac_register_f64, include/epn_so3conv.h; no counterpart in the reference -- the host tool for this step is open3d's
+    registration_ransac_based_on_feature_matching)."""
+    lib = _lib.get_lib()
+    _lib.same_device(all_kps, match_src)
+    k = _lib.dev_ptr(all_kps, "all_kps")
+    if all_kps.dim() != 2 or all_kps.shape[1] != 3:
+        raise ValueError(f"all_kps must be [R,3], got {tuple(all_kps.shape)}")
+    H = int(hypotheses)
+    if not 1 <= H <= 65536:
+        raise ValueError(f"hypotheses must be in 1..65536, got {hypotheses}")
+    if not (np.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"tau must be finite and > 0, got {tau}")
+    if not 0.0 <= min_margin < 1.0:
+        raise ValueError(f"min_margin must be in [0, 1), got {min_margin}")
+    host, dev = _scene_tables(frag_off, pairs, all_kps.device)
+    n_tgt, P = int(host["tgt_off"][-1]), host["pairs"].shape[0]
+    if not np.array_equal(np.asarray(tgt_off, dtype=np.int64).reshape(-1), host["tgt_off"]):
+        raise ValueError("tgt_off does not belong to these pairs")
+    if match_src.shape != (n_tgt,):
+        raise ValueError(f"match_src must be [{n_tgt}] for these pairs, got {tuple(match_src.shape)}")
+    f64, i32 = dict(dtype=torch.float64, device=all_kps.device), dict(dtype=torch.int32, device=all_kps.device)
+    T, best_h, hyp_count = torch.empty((P, 4, 4), **f64), torch.empty((P,), **i32), torch.empty((P, H), **i32)
+    n_inlier, rmse, margin = torch.empty((P,), **i32), torch.empty((P,), **f64), torch.empty((P,), **f64)
+    ws_bytes = int(lib.epn_ransac_register_workspace_bytes(n_tgt))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=all_kps.device)
+    _lib.check(lib.epn_ransac_register_f64(k, all_kps.shape[0], host["frag_off"].size - 1, *_table_args(host, dev, "frag_off"), P,
+                                           *_table_args(host, dev, "pairs", "tgt_off"),
+                                           _lib.dev_ptr(match_src, "match_src", torch.int32), float(tau), H,
+                                           int(seed) & (2 ** 64 - 1), int(pair0), float(min_margin),
+                                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, _lib.dev_ptr(T, "T", torch.float64),
+                                           _lib.dev_ptr(best_h, "best_h", torch.int32),
+                                           _lib.dev_ptr(hyp_count, "hyp_count", torch.int32),
+                                           _lib.dev_ptr(n_inlier, "n_inlier", torch.int32),
+                                           _lib.dev_ptr(rmse, "rmse", torch.float64),
+                                           _lib.dev_ptr(margin, "margin", torch.float64), _lib.stream_of(all_kps)),
+               "ransac_register")
+    return T, best_h, hyp_count, n_inlier, rmse, margin
+
+
 def initial_anchor_query(centers, xyz, kernel_points, radius, sigma):
     """(centers f[b,3,nc], xyz f[m,3], kernel_points f[ks,na,3], radius, sigma) ->
     [anchor_weights f[b,ks,nc,na], anchor_ctn f[b,ks,nc,na]]  (grouping_cuda.cpp:138-158; KernelPropagation).  float32 or

@@ -132,7 +132,7 @@ int epn_radius_patches_f32(const float *pc, int n, const float *kpts, int k, int
  * block of the reference's evaluation (SPConvNets/datasets/evaluation_3dmatch.py:77-100: two sklearn KDTrees, the mutual
  * mask, hom_transform, distances < tau1); this is the library's own deterministic statement of it.
  *
- * Scene tables (shared by the two entries below):
+ * Scene tables (shared by the two entries below and by epn_ransac_register_f64):
  *   frag_off i64[F+1]  row offsets of the fragments in the concatenated arrays: frag_off[0] = 0, ascending (an empty
  *                      fragment is allowed), frag_off[F] = R, fewer than 2^31 rows per fragment
  *   pairs    i32[P,2]  (src fragment, tgt fragment), both in 0..F-1, src != tgt, P <= 32767
@@ -175,6 +175,48 @@ int epn_match_inliers_f64(const float *kp_xyz, int64_t R, int F, const int64_t *
                           const int64_t *tgt_off_host, const int64_t *tgt_off, const int32_t *nn_idx, const double *gt,
                           double tau1, int32_t *match_src, double *match_dist, int32_t *n_match, int32_t *n_inlier,
                           epn_stream_t stream);
+
+/* Pairwise registration: the rigid transform between the two fragments of every pair of a scene from its mutual matches alone,
+ * by hypothesise-and-verify (RANSAC) over three-point samples and one least-squares refit.  No ground truth
+ * enters.  The reference stops at feature-match recall; the host tool usually run for this step is open3d's
+ * registration_ransac_based_on_feature_matching.  This is the library's own deterministic statement of it.
+ *
+ * epn_ransac_register_f64: the scene tables frag_off, pairs and tgt_off of the matching entries above (host and device copy
+ *   each, the same refusal rules); kp_xyz f32[R,3]; match_src i32[tgt_off[P]] as epn_match_inliers_f64 writes it (-1 = not
+ *   mutual); tau f64, finite and > 0; H hypotheses per pair, 1 <= H <= 65536; seed u64; pair0 >= 0, the counter word of
+ *   pairs[0] (pair p of the call draws as pair pair0 + p, so a pair gives the same result alone and in a batch);
+ *   min_margin f64, 0 <= min_margin < 1.
+ *   Correspondences of pair p: its tgt rows j with 0 <= s = match_src[j] < n_src(p), numbered m = 0..M_p-1 in ascending j;
+ *     x_m = kp_src[s], y_m = kp_tgt[j], widened to fp64.  match_src is range-checked on the device: an entry >= n_src(p) is
+ *     dropped like a negative one and never used as an index.
+ *   Draw: hypothesis h takes i_k = word_k(Philox4x32-10(ctr_lo = h, ctr_hi = pair0 + p, key = seed)) mod M_p, k = 0, 1, 2 (a
+ *     modulo bias of about M_p / 2^32, as in epn_radius_patches_f32).  It is REJECTED if M_p < 3 or two i_k are equal.
+ *   Fit of a set S (Horn), fp64: centroids xbar, ybar over S; C = sum_{m in S} (x_m - xbar)(y_m - ybar)^T; (R, margin) = the
+ *     projection of epn_so3_mean_f32 above applied to C (R maximises tr(R^T C), margin = (s2 + d s3) / s1); t = xbar - R ybar.
+ *     (R, t) takes tgt coordinates into src coordinates, the direction of gt in epn_match_inliers_f64.  A hypothesis whose
+ *     three-point fit has margin < min_margin is rejected too (collinear or coincident samples have margin 0).
+ *   Score: count[h] = #{m : |x_m - (R y_m + t)|^2 < tau^2} in fp64 over all M_p correspondences; -1 for a rejected hypothesis.
+ *   Choice: best_h = the h with the largest count, the lowest h on a tie.  The pair FAILS if count[best_h] < 3 (which includes
+ *     every hypothesis rejected): T = I, best_h = -1, n_inlier = 0, rmse = +inf, margin = 0.
+ *   Refit: one fit over the inlier set of best_h.  That fit is the result; its margin is reported, not tested (always a
+ *     rotation, conditioning reported, as epn_so3_mean_f32).  n_inlier and rmse = sqrt(mean of the squared inlier distances)
+ *     are taken again under the refitted transform; rmse = +inf when that set is empty.
+ *   Outputs: T f64[P,4,4] row-major with bottom row 0 0 0 1; best_h i32[P]; hyp_count i32[P,H], every hypothesis' score (an
+ *     output, not scratch: it is what makes the entry testable); n_inlier i32[P]; rmse f64[P]; margin f64[P].
+ *   Workspace: epn_ransac_register_workspace_bytes(tgt_off[P]) bytes (host-only: 24 bytes per tgt row for the compacted
+ *     correspondences, rounded up to 8, plus 4 bytes for each of the 32768 pair counts), 8-byte aligned; written by the call.
+ *   Three launches (compact, score, finish: csrc/ransac_register.hip); no atomics; the refit's sums run in a fixed order
+ *   (thread i adds m = i, i + 256, ... ascending, then a fixed tree), so two runs are bitwise equal.  Every loop is bounded by
+ *   a row count, M_p, H or the projection's sweep count.
+ *   Refusals, decided before any HIP runtime call: EPN_EINVAL for H, tau, min_margin or pair0 out of range (NaN included), then
+ *   the scene-table refusals; P == 0 succeeds and launches nothing; then EPN_ENULL for a required pointer that is NULL
+ *   (kp_xyz and match_src only if there is a tgt row), EPN_EWORKSPACE for a workspace that is NULL or too small. */
+size_t epn_ransac_register_workspace_bytes(int64_t tgt_rows);
+int epn_ransac_register_f64(const float *kp_xyz, int64_t R, int F, const int64_t *frag_off_host, const int64_t *frag_off, int P,
+                            const int32_t *pairs_host, const int32_t *pairs, const int64_t *tgt_off_host, const int64_t *tgt_off,
+                            const int32_t *match_src, double tau, int H, uint64_t seed, int64_t pair0, double min_margin,
+                            void *workspace, size_t workspace_bytes, double *T, int32_t *best_h, int32_t *hyp_count,
+                            int32_t *n_inlier, double *rmse, double *margin, epn_stream_t stream);
 
 /* Voxel-grid downsampling: one centroid per occupied voxel of ONE fragment.  The reference never searches the raw fragment:
  * radius_ball_search_o3d (SPConvNets/datasets/match_3dmatch.py:107-139) calls open3d's pcd.voxel_down_sample(voxel_size)
