@@ -180,17 +180,19 @@ __device__ __forceinline__ void scatter_segment(const InterArgs &A, const Seg<NT
 // ------------------------------------------------------------------------------------ backward (data)
 // dG[ck][col] = sum_o W[o][ck] dOut[col][o]   (M = ck, N = col, contraction o; WT staged by o-groups)
 // T[n][c]     = sum_k w[n][k] dG[c,k]         per column, then  dF[b, idx[n], a, c] += T[n][c]
-template <int NT, int KT>
+// TIGHT (ks = 32 only): both LDS tiles without their 4-float row padding -- 4 x 16 x 512 + 512 x 16 floats are exactly the
+// 160 KB of a workgroup, the padded tiles (169 KB) do not fit.  Bank conflicts instead of no kernel.
+template <int NT, int KT, bool TIGHT = false>
 __global__ __launch_bounds__(64 * NW) void inter_bwd_data_kernel(InterArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int x = lane & 15, j = lane >> 4;
     const int ckl = 16 * A.ks;
-    const int gss = ckl + 4;
+    const int gss = ckl + (TIGHT ? 0 : 4);
     float *Gs = smem + (size_t)wave * 16 * gss;   // dG tile of this wave: [col][c_local*ks + k]
     float *Ws = smem + (size_t)NW * 16 * gss;     // WT rows [ckl][16(+4)] for one group of 16 output channels
-    const int wss = 20;
+    constexpr int wss = TIGHT ? 16 : 20;
     const int MTK = ckl >> 4;                     // 16-row tiles of the chunk (24 for ks = 24)
     const long long col0 = ((long long)blockIdx.x * NW + wave) * 16;
     const bool active = col0 < A.ncol;
@@ -691,10 +693,11 @@ __global__ __launch_bounds__(64 * NW8) void inter_bwd_data8_kernel(InterArgs A) 
     const int tile = wave >> 1, half = wave & 1;
     const int x = lane & 15, j = lane >> 4;
     const int ckl = 16 * A.ks;
-    const int gss = ckl + 4;
+    constexpr bool TIGHT = MH == 16;   // ks = 32: unpadded tiles, exactly 160 KB (see inter_bwd_data_kernel)
+    const int gss = ckl + (TIGHT ? 0 : 4);
     float *Gs = smem + (size_t)tile * 16 * gss;
     float *Ws = smem + (size_t)4 * 16 * gss;
-    const int wss = 20;
+    constexpr int wss = TIGHT ? 16 : 20;
     const int m0 = half * MH;
     const long long col0 = ((long long)epn_xcd_tile(blockIdx.x, gridDim.x) * 4 + tile) * 16;
     const bool active = col0 < A.ncol;
@@ -1771,10 +1774,13 @@ int launch_inter_fwd_mfma(const epn_inter_desc *d, const float *rk4, const float
         return 0;
     }
     const int ckl = 16 * d->ks;
-    // W sub-chunk width: largest divisor of the chunk length (multiple of 16) that keeps Ws <= ~56 KB
+    // W sub-chunk width: largest divisor of the chunk length (multiple of 16) that keeps Ws <= ~56 KB -- and inside what the
+    // grouped-feature tiles leave of the 160 KB (ks = 28: 47 KB, ks = 32: 31 KB; wk = 16 always fits)
+    const size_t ws_left = (size_t)160 * 1024 - gs_bytes(d);
+    const size_t ws_budget = ws_left < 56 * 1024 ? ws_left : 56 * 1024;
     int wk = 16;
     for (int cand = 16; cand <= ckl; cand += 16)
-        if (ckl % cand == 0 && (size_t)d->cout * (cand + 4) * sizeof(float) <= 56 * 1024 &&
+        if (ckl % cand == 0 && (size_t)d->cout * (cand + 4) * sizeof(float) <= ws_budget &&
             d->cout * cand <= 256 * WPF * 4)
             wk = cand;
     A.wk = wk;
@@ -1804,7 +1810,8 @@ int launch_inter_bwd_data_mfma(const epn_inter_desc *d, const float *rk4, const 
     A.W = wt; A.gout = dOut; A.out = dF;
     {
         if (d->na >= 16 && d->nn <= 32 && (d->ks == 24 || d->ks == 32 || d->ks == 16)) {
-            const size_t lds8 = (size_t)4 * 16 * (16 * d->ks + 4) * sizeof(float) + (size_t)16 * d->ks * 20 * sizeof(float);
+            const int pad8 = d->ks == 32 ? 0 : 4;   // MH = 16: unpadded tiles
+            const size_t lds8 = (size_t)4 * 16 * (16 * d->ks + pad8) * sizeof(float) + (size_t)16 * d->ks * (16 + pad8) * sizeof(float);
             const unsigned grid8 = (unsigned)((A.ncol + 63) / 64);
 #define EPN_BD8(NT_, KT_, MH_)                                                                                 \
     do {                                                                                                       \
@@ -1822,15 +1829,25 @@ int launch_inter_bwd_data_mfma(const epn_inter_desc *d, const float *rk4, const 
             return 0;
         }
     }
-    const size_t lds = gs_bytes(d) + (size_t)16 * d->ks * 20 * sizeof(float);
+    const bool tight = d->ks == 32;
+    const size_t lds = tight ? (size_t)NW * 16 * 16 * d->ks * sizeof(float) + (size_t)16 * d->ks * 16 * sizeof(float)
+                             : gs_bytes(d) + (size_t)16 * d->ks * 20 * sizeof(float);
     const unsigned grid = (unsigned)((A.ncol + 16 * NW - 1) / (16 * NW));
-#define EPN_BD(NT_, KT_, dummy)                                                                       \
-    do {                                                                                              \
-        int rc_ = set_lds(inter_bwd_data_kernel<NT_, KT_>, lds);                                      \
-        if (rc_) return rc_;                                                                          \
-        EPN_LAUNCH((inter_bwd_data_kernel<NT_, KT_>), dim3(grid), dim3(64 * NW), lds, st, A); \
+#define EPN_BD(NT_, KT_, TIGHT_)                                                                              \
+    do {                                                                                                      \
+        int rc_ = set_lds(inter_bwd_data_kernel<NT_, KT_, TIGHT_>, lds);                                      \
+        if (rc_) return rc_;                                                                                  \
+        EPN_LAUNCH((inter_bwd_data_kernel<NT_, KT_, TIGHT_>), dim3(grid), dim3(64 * NW), lds, st, A); \
     } while (0)
-    EPN_DISPATCH_NT_KT(EPN_BD, 0);
+    if (tight) {
+        const int nt_ = (d->nn + 15) / 16;
+        if (nt_ <= 1) EPN_BD(1, 2, true);
+        else if (nt_ <= 2) EPN_BD(2, 2, true);
+        else if (nt_ <= 4) EPN_BD(4, 2, true);
+        else EPN_BD(8, 2, true);
+    } else {
+        EPN_DISPATCH_NT_KT(EPN_BD, false);
+    }
 #undef EPN_BD
     EPN_CHECK_LAUNCH();
     return 0;

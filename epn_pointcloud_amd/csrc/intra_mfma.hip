@@ -221,7 +221,7 @@ __global__ __launch_bounds__(768) void intra_bwd_weight_pt_kernel(IntraArgs A, l
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
         const int a = 4 * s + j;
-        srow[s] = (s < nsteps && a < A.na) ? A.idx[a * A.kn + k] : 0;
+        srow[s] = (s < nsteps && a < A.na && k < A.kn) ? A.idx[a * A.kn + k] : 0;   // (kn < 8: waves kn .. 7 only stage)
     }
 
     f32x4 acc[4][4];
