@@ -44,7 +44,10 @@ struct SbArgs {
 };
 
 // per-lane normalisation of its 4 channels: n = (v - mean) * rstd * gamma + beta, leaky (the formula of glue.hip's
-// norm_act_fwd_kernel, so folded and unfolded paths agree to the last bit)
+// norm_act_fwd_kernel).  Folded and unfolded path agree to the last bit with frozen statistics and with bf16 storage; with
+// batch / instance statistics and fp32 storage they differ by a few ulp in some elements (CHANGELOG has the figures) --
+// presumably mean / var / rstd from (s1, s2), compiled separately here (sb_norm_load) and there (stats4); not verified in the
+// ISA.  tests/test_gpu_basis_exact.py holds both to the float64 norm within the bound of the glue's forward pass.
 struct SbNorm {
     float mean[4], rstd[4], ga[4], be[4];
     float slope;
@@ -590,7 +593,10 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
             if (A.dstat_x) sb_point_dstats<false>(acc, A, tab, rxs, upt, cho, pt, choff0, choff, cval, j);
             else if (A.pstats) sb_point_stats<false>(acc, A.pstats, pt, A.c, choff0, cval, j);
         } else if (A.pstats) sb_point_stats<false>(acc, A.pstats, pt, A.c, choff0, cval, j);
-        if (A.amax) {                     // rows >= na and lanes without channels hold zeros: no masking needed
+        // rows >= na hold zeros (M is zero padded).  Lanes without channels do NOT under norm on load: their zero rows went
+        // through sb_norm1 with the statistics of point 0, channels 0..3, so their accumulators hold leaky(norm(0)) * rowsum(M),
+        // which is never stored -- such a lane contributes nothing to the maximum (the select after the scan)
+        if (A.amax) {
             float tmax = 0.0f;            // (fmaxf drops NaNs by itself)
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
@@ -614,7 +620,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
                             tmax = __builtin_fmaxf(tmax, v <= 3.4028235e38f ? v : 0.0f);
                         }
             }
-            vmax = __builtin_fmaxf(vmax, tmax);
+            vmax = cval ? __builtin_fmaxf(vmax, tmax) : vmax;
         }
         // acc[mt][nt][rr]: output row 16 mt + 4 j + rr, channel 4 x + nt
 #pragma unroll
@@ -804,8 +810,9 @@ static int so3_basis_any(const void *in, const float *M, const int32_t *blocks, 
     const dim3 grid((unsigned)((tasks + per_wg - 1) / per_wg));
     // 32-bit row offsets + buffer instructions when the tensor is below 2 GiB and the per-point strides fit 24 bits
     const long long bytes = pts * na * c * (bf16 == 1 ? 2LL : 4LL);
-    if (dstat_x && (!(bytes < 0x7fffff00LL && pts < (1LL << 24)) || !point_stats || !nh || out_spectral)) return EPN_EINVAL;
     const bool small_t = bytes < 0x7fffff00LL && pts < (1LL << 24) && (long long)na * c * 4 < (1LL << 24);
+    // dstat_x exists in the 32-bit forms only: the 64-bit kernels would write plain (sum, sum of squares) into point_dstats
+    if (dstat_x && (!small_t || !point_stats || !nh || out_spectral)) return EPN_EINVAL;
     if (nh && nh->frozen) {
         if (dstat_x || point_stats || amax_out || nh->groups != 1) return EPN_EINVAL;
         if (bf16 == 1) {
@@ -883,7 +890,8 @@ extern "C" int epn_so3_basis_stats_bf16(const void *in, const float *M, const in
 // Inverse transform of a spectral GRADIENT + the block partials of the backward reduction of the norm that preceded the
 // forward transform (SbArgs::dstat_x): dy = U . grad (plain layout), point_dstats[pt][c][2] = (sum d, sum d xhat) over the
 // point's anchors with d = dy * leaky'(norm(x)).  epn_norm_bwd_finish turns the partials into dsums / dgamma / dbeta.
-// Tensors of 2 GiB or more: EPN_EINVAL (use epn_so3_basis_* + epn_norm_act_bwd_reduce_*).
+// Shapes the 32-bit-offset kernels do not take (2 GiB or more, or na * c * 4 >= 2^24): EPN_EINVAL (use epn_so3_basis_* +
+// epn_norm_act_bwd_reduce_*).
 static int so3_basis_dstats_any(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c, void *out,
                                 const void *x_cl, const float *sums, int groups, long long pts_per_group, const float *gamma,
                                 const float *beta, float eps, float slope, float *point_dstats, int bf16, epn_stream_t stream) {

@@ -701,7 +701,9 @@ int epn_so3_basis_f32(const float *in, const float *M, const int32_t *blocks, lo
  * base * cin * cout as a row-major [d*cin][d*cout] matrix; what_t: the same blocks transposed ([d*cout][d*cin], the Bt
  * operand of epn_gemm_nt for the forward product); either may be NULL.  epn_spectral_weights_bwd_f32 is the transpose
  * (grad_W[o][c][k] from grad_what in the `what` layout).  Replaces nothing in the reference (the spectral form is this
- * library's); it replaces ~25 small torch launches per layer and direction. */
+ * library's); it replaces ~25 small torch launches per layer and direction.  A block dimension above 7 is NOT
+ * supported: the kernels recover d from blocks[f][1] = d*d through a ladder that ends at 7 (1 + 9 + 9 + 16 + 25 of the
+ * icosahedral group needs 5), and the entries do not check it. */
 int epn_spectral_weights_f32(const float *W, const float *R, const int32_t *blocks, int cout, int cin, int kn, int na,
                              float *what, float *what_t, epn_stream_t stream);
 /* the same blocks rounded to bf16 (fp32 master weights -> the operands of a bf16 network's GEMMs) */
@@ -1009,8 +1011,9 @@ int epn_so3_basis_norm_frozen_bf16(const void *in, const float *M, const int32_t
  * of the tensor x_cl the forward transform normalised (sums / groups / pts_per_group / gamma / beta / eps / slope as for
  * epn_so3_basis_norm_*).  epn_norm_bwd_finish reduces block partials part[g][block][c][2] to the dsums[g][c][2], dgamma[c],
  * dbeta[c] that epn_norm_act_bwd_apply_* takes (workspace: epn_stats_finish_workspace_bytes(groups, blocks_per_group, c));
- * together they replace epn_norm_act_bwd_reduce_* (one full read of x and dy) for that norm.  Tensors of 2 GiB or more:
- * EPN_EINVAL (keep the separate reduction). */
+ * together they replace epn_norm_act_bwd_reduce_* (one full read of x and dy) for that norm.  Tensors of 2 GiB or more, 2^24
+ * points or more, or a point of na * c * 4 >= 2^24 bytes (the shapes the 32-bit-offset kernels do not take): EPN_EINVAL,
+ * nothing is written (keep the separate reduction). */
 int epn_so3_basis_dstats_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c, float *out,
                              const float *x_cl, const float *sums, int groups, long long pts_per_group, const float *gamma,
                              const float *beta, float eps, float slope, float *point_dstats, epn_stream_t stream);
