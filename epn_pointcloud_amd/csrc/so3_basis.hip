@@ -229,9 +229,106 @@ __device__ __forceinline__ void sb_point_dstats(const f32x4 (&acc)[4][4], const 
     }
 }
 
+// ---- the task skeleton of the three basis-change kernels below.  Only the contraction differs between them (how M sits in
+// LDS and how the rows become MFMA operands); what surrounds it is here, once.  Set-up pieces and the amax scan are functions.
+// The pieces that work on a task's locals (decode, epilogue statistics, store loop) are statement macros expanded in the
+// kernel's own scope: as inlined functions over a task struct every form tried gave the twelve instances other schedules and
+// register counts (CHANGELOG), as macros the machine code is that of the three hand-written copies.
+
+// bs[r] / d2s[r]: base row and d * d of spectral row r's irreducible block (rows >= na: those of row 0, never addressed)
+__device__ __forceinline__ void sb_fill_blocks(const SbArgs &A, int *bs, int *d2s) {
+    if (threadIdx.x < 64) {
+        const int f = threadIdx.x < A.na ? threadIdx.x : 0;
+        bs[threadIdx.x] = A.blk[2 * f];
+        d2s[threadIdx.x] = A.blk[2 * f + 1];
+    }
+}
+// buffer resource over one [pts][na][c] tensor of ESZ-byte elements (used by the SMALL forms only)
+template <int ESZ, bool SMALL>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t sb_rsrc(const SbArgs &A, const void *p) {
+    const unsigned nbytes = SMALL ? (unsigned)(A.pts * A.na * A.c * (long long)ESZ) : 0u;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)nbytes, 0x00020000);
+}
+__device__ __forceinline__ void sb_zero(f32x4 (&acc)[4][4]) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// Task `it` of wave `wave` (needs A, bs, d2s, ncb, wave, it, x; LEAVE: `return` or `break` past the last task): one (point,
+// 64-channel block), lane column x = channels choff0 .. choff0 + 3 of it; defines pt, choff0, cval (this lane's 4 channels
+// exist), choff (= choff0, 0 without channels) and row_addr(spec, r), the element offset of row r of the point (64-bit forms).
+// c == 32 (the first two blocks of the rotation / 3DMatch networks): a 64-channel block would leave lanes x >= 8 idle
+// (round 3: "half empty"); instead a task is TWO points, lanes x >= 8 carry the second one -- only the per-lane point
+// index of the loads, stores and statistics changes, M is the same for every column
+#define SB_DECODE_TASK(LEAVE)                                                                                           \
+    const long long task = ((long long)blockIdx.x * SB_WAVES + wave) * SB_TPW + it;                                     \
+    const bool pair = SMALL && A.pair;                                                                                  \
+    if (task >= (pair ? (A.pts + 1) >> 1 : A.pts * ncb)) LEAVE;                                                         \
+    const long long pt = pair ? 2 * task + (x >> 3) : task / ncb;                                                       \
+    const int cb = pair ? 0 : (int)(task - pt * ncb);                                                                   \
+    const int choff0 = pair ? 4 * (x & 7) : 64 * cb + 4 * x;                                                            \
+    const bool cval = pair ? pt < A.pts : choff0 < A.c;                                                                 \
+    const int choff = cval ? choff0 : 0;                                                                                \
+    auto row_addr = [&](int spec, int r) -> size_t {                                                                    \
+        if (spec) return ((size_t)bs[r] * A.pts + (size_t)pt * d2s[r] + (r - bs[r])) * A.c + choff;                     \
+        return ((size_t)pt * A.na + r) * A.c + choff;                                                                   \
+    }
+// the dstats / stats / none choice of the epilogue (BF: the output is stored as bf16, the statistics are those of the rounded
+// values); needs the task's locals and acc, tab, rxs, upt, cho, j
+#define SB_EPILOGUE_STATS(BF)                                                                                           \
+    if constexpr (SMALL) {                                                                                              \
+        if (A.dstat_x) sb_point_dstats<BF>(acc, A, tab, rxs, upt, cho, pt, choff0, choff, cval, j);                     \
+        else if (A.pstats) sb_point_stats<BF>(acc, A.pstats, pt, A.c, choff0, cval, j);                                 \
+    } else if (A.pstats) sb_point_stats<BF>(acc, A.pstats, pt, A.c, choff0, cval, j)
+// acc[mt][nt][rr]: output row 16 mt + 4 j + rr, channel 4 x + nt.  The s_nop stays directly behind the last store: the
+// store data registers are the next task's accumulators
+#define SB_STORE_ROWS(T)                                                                                                \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                                                    \
+        _Pragma("unroll") for (int rr = 0; rr < 4; ++rr) {                                                              \
+            const int r = 16 * mt + 4 * j + rr;                                                                         \
+            const f32x4 v = {acc[mt][0][rr], acc[mt][1][rr], acc[mt][2][rr], acc[mt][3][rr]};                           \
+            if constexpr (SMALL) sb_bst(static_cast<T *>(nullptr), rout, sb_off(tab.rbo, tab.rso, r, upt, cho), v);     \
+            else if (r < A.na && cval) sb_st(static_cast<T *>(A.out) + row_addr(A.out_spec, r), v);                     \
+        }                                                                                                               \
+    if constexpr (SMALL) asm volatile("s_nop 4" ::: "memory")
+
+// max |output| of one task into the lane's running maximum (SbArgs::amax; the split form only).
+// Rows >= na hold zeros (M is zero padded).  Lanes without channels do NOT under norm on load: their zero rows went
+// through sb_norm1 with the statistics of point 0, channels 0..3, so their accumulators hold leaky(norm(0)) * rowsum(M),
+// which is never stored -- such a lane contributes nothing to the maximum (the select after the scan)
+__device__ __forceinline__ float sb_amax_scan(const f32x4 (&acc)[4][4], bool cval, float vmax) {
+    float tmax = 0.0f;            // (fmaxf drops NaNs by itself)
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+            tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, __builtin_fmaxf(__builtin_fabsf(acc[mt][nt][0]), __builtin_fabsf(acc[mt][nt][1]))),
+                                   __builtin_fmaxf(__builtin_fabsf(acc[mt][nt][2]), __builtin_fabsf(acc[mt][nt][3])));
+    // An infinite output is left OUT of the maximum, as absmax4 / split_rows2 leave non-finite elements out (advisor
+    // finding, round 5: clamped to FLT_MAX it became the scale, 2^-113, and every finite element of the buffer
+    // underflowed to zero in the consuming GEMMs; an fp32 GEMM poisons only the rows the element belongs to).  The
+    // masked rescan runs only in a wave that saw one.
+    if (__builtin_amdgcn_ballot_w64(tmax > 3.4028235e38f) != 0ull) {
+        tmax = 0.0f;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const float v = __builtin_fabsf(acc[mt][nt][rr]);
+                    tmax = __builtin_fmaxf(tmax, v <= 3.4028235e38f ? v : 0.0f);
+                }
+    }
+    return cval ? __builtin_fmaxf(vmax, tmax) : vmax;
+}
+
 // (FROZEN, here and in the two kernels below: the norm on load reads frozen statistics, sb_norm_load; the trailing `true` of an
 // instance's name.  A template parameter of the kernel itself: as a device function under two kernels the body was scheduled
 // differently from the kernel it had been.)
+// T: float only (the instance names carry it); bf16 storage has so3_basis_bf16_kernel
 template <typename T, bool SMALL, bool FROZEN = false>
 __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_kernel(SbArgs A) {
     __shared__ float Ms[64 * SB_LD];
@@ -241,51 +338,26 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_kernel(SbArgs A) {
         const int r = i >> 6, s = i & 63;
         Ms[r * SB_LD + s] = (r < A.na && s < A.na) ? A.M[r * A.na + s] : 0.0f;
     }
-    if (threadIdx.x < 64) {
-        const int f = threadIdx.x < A.na ? threadIdx.x : 0;
-        bs[threadIdx.x] = A.blk[2 * f];
-        d2s[threadIdx.x] = A.blk[2 * f + 1];
-    }
-    if constexpr (SMALL) sb_make_tables<(int)sizeof(T)>(A, tab);
+    sb_fill_blocks(A, bs, d2s);
+    if constexpr (SMALL) sb_make_tables<4>(A, tab);
     __syncthreads();
-    const unsigned nbytes = SMALL ? (unsigned)(A.pts * A.na * A.c * (long long)sizeof(T)) : 0u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(A.in), 0, (int)nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(A.out, 0, (int)nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rxs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(A.dstat_x ? A.dstat_x : A.in), 0, (int)nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = sb_rsrc<4, SMALL>(A, A.in), rout = sb_rsrc<4, SMALL>(A, A.out);
+    const __amdgpu_buffer_rsrc_t rxs = sb_rsrc<4, SMALL>(A, A.dstat_x ? A.dstat_x : A.in);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int x = lane & 15, j = lane >> 4;
     const int ncb = (A.c + 63) >> 6;      // c % 32 == 0: the last block of a 32 (mod 64) width is half empty (lanes x >= 8)
     const int nst = A.na >> 2;        // contraction steps of 4 rows (na % 4 == 0, launcher)
     for (int it = 0; it < SB_TPW; ++it) {
-        const long long task = ((long long)blockIdx.x * SB_WAVES + wave) * SB_TPW + it;
-        // c == 32 (the first two blocks of the rotation / 3DMatch networks): a 64-channel block would leave lanes x >= 8 idle
-        // (round 3: "half empty"); instead a task is TWO points, lanes x >= 8 carry the second one -- only the per-lane point
-        // index of the loads, stores and statistics changes, M is the same for every column
-        const bool pair = SMALL && A.pair;
-        if (task >= (pair ? (A.pts + 1) >> 1 : A.pts * ncb)) return;
-        const long long pt = pair ? 2 * task + (x >> 3) : task / ncb;
-        const int cb = pair ? 0 : (int)(task - pt * ncb);
-        const int choff0 = pair ? 4 * (x & 7) : 64 * cb + 4 * x;
-        const bool cval = pair ? pt < A.pts : choff0 < A.c;        // this lane's 4 channels exist
-        const int choff = cval ? choff0 : 0;
-
-        auto row_addr = [&](int spec, int r) -> size_t {   // float offset of row r of this point
-            if (spec) return ((size_t)bs[r] * A.pts + (size_t)pt * d2s[r] + (r - bs[r])) * A.c + choff;
-            return ((size_t)pt * A.na + r) * A.c + choff;
-        };
-
+        SB_DECODE_TASK(return);
         f32x4 acc[4][4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const unsigned cho = cval ? (unsigned)choff0 * (unsigned)sizeof(T) : SB_CHO_OOB, upt = (unsigned)pt;
+        sb_zero(acc);
+        const unsigned cho = cval ? (unsigned)choff0 * 4u : SB_CHO_OOB, upt = (unsigned)pt;
         f32x4 bv[16];
 #pragma unroll
         for (int st = 0; st < 16; ++st)
             if (st < nst) {
-                if constexpr (SMALL && sizeof(T) == 4) bv[st] = sb_bld128(rin, sb_off(tab.rbi, tab.rsi, 4 * st + j, upt, cho));
+                if constexpr (SMALL) bv[st] = sb_bld128(rin, sb_off(tab.rbi, tab.rsi, 4 * st + j, upt, cho));
                 else bv[st] = cval ? sb_ld(static_cast<const T *>(A.in) + row_addr(A.in_spec, 4 * st + j)) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
         if (A.nsums && !A.dstat_x) {
@@ -295,11 +367,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_kernel(SbArgs A) {
             for (int st = 0; st < 16; ++st)
                 if (st < nst) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float n = sb_norm1(N, i, bv[st][i]);
-                        if constexpr (sizeof(T) == 2) n = (float)(__bf16)n;    // what the unfolded path stores and re-reads
-                        bv[st][i] = n;
-                    }
+                    for (int i = 0; i < 4; ++i) bv[st][i] = sb_norm1(N, i, bv[st][i]);
                 }
         }
 #pragma unroll
@@ -313,21 +381,8 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_kernel(SbArgs A) {
                 }
             }
         }
-        if constexpr (SMALL) {
-            if (A.dstat_x) sb_point_dstats<sizeof(T) == 2>(acc, A, tab, rxs, upt, cho, pt, choff0, choff, cval, j);
-            else if (A.pstats) sb_point_stats<sizeof(T) == 2>(acc, A.pstats, pt, A.c, choff0, cval, j);
-        } else if (A.pstats) sb_point_stats<sizeof(T) == 2>(acc, A.pstats, pt, A.c, choff0, cval, j);
-        // acc[mt][nt][rr]: output row 16 mt + 4 j + rr, channel 4 x + nt
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int r = 16 * mt + 4 * j + rr;
-                const f32x4 v = {acc[mt][0][rr], acc[mt][1][rr], acc[mt][2][rr], acc[mt][3][rr]};
-                if constexpr (SMALL) sb_bst(static_cast<T *>(nullptr), rout, sb_off(tab.rbo, tab.rso, r, upt, cho), v);
-                else if (r < A.na && cval) sb_st(static_cast<T *>(A.out) + row_addr(A.out_spec, r), v);
-            }
-        if constexpr (SMALL) asm volatile("s_nop 4" ::: "memory");   // store data registers are the next task's accumulators
+        SB_EPILOGUE_STATS(false);
+        SB_STORE_ROWS(T);
     }
 }
 
@@ -348,10 +403,8 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_bf16_kernel(SbArgs A)
     __shared__ int bs[64], d2s[64];
     __shared__ SbTables tab;
     if constexpr (SMALL) sb_make_tables<2>(A, tab);
-    const unsigned nbytes = SMALL ? (unsigned)(A.pts * A.na * A.c * 2LL) : 0u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(A.in), 0, (int)nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(A.out, 0, (int)nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rxs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(A.dstat_x ? A.dstat_x : A.in), 0, (int)nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = sb_rsrc<2, SMALL>(A, A.in), rout = sb_rsrc<2, SMALL>(A, A.out);
+    const __amdgpu_buffer_rsrc_t rxs = sb_rsrc<2, SMALL>(A, A.dstat_x ? A.dstat_x : A.in);
     for (int i = threadIdx.x; i < 64 * 64; i += blockDim.x) {
         const int r = i >> 6, q = i & 63;
         const float m = (r < A.na && q < A.na) ? A.M[r * A.na + q] : 0.0f;
@@ -359,34 +412,15 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_bf16_kernel(SbArgs A)
         Mh[r * SBH_LD + q] = hi;
         Ml[r * SBH_LD + q] = (__bf16)(m - (float)hi);
     }
-    if (threadIdx.x < 64) {
-        const int f = threadIdx.x < A.na ? threadIdx.x : 0;
-        bs[threadIdx.x] = A.blk[2 * f];
-        d2s[threadIdx.x] = A.blk[2 * f + 1];
-    }
+    sb_fill_blocks(A, bs, d2s);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int x = lane & 15, j = lane >> 4;
     const int ncb = (A.c + 63) >> 6;      // c % 32 == 0: the last block of a 32 (mod 64) width is half empty (lanes x >= 8)
     const __bf16 *in = static_cast<const __bf16 *>(A.in);
-    __bf16 *out = static_cast<__bf16 *>(A.out);
     for (int it = 0; it < SB_TPW; ++it) {
-        const long long task = ((long long)blockIdx.x * SB_WAVES + wave) * SB_TPW + it;
-        // c == 32 (the first two blocks of the rotation / 3DMatch networks): a 64-channel block would leave lanes x >= 8 idle
-        // (round 3: "half empty"); instead a task is TWO points, lanes x >= 8 carry the second one -- only the per-lane point
-        // index of the loads, stores and statistics changes, M is the same for every column
-        const bool pair = SMALL && A.pair;
-        if (task >= (pair ? (A.pts + 1) >> 1 : A.pts * ncb)) return;
-        const long long pt = pair ? 2 * task + (x >> 3) : task / ncb;
-        const int cb = pair ? 0 : (int)(task - pt * ncb);
-        const int choff0 = pair ? 4 * (x & 7) : 64 * cb + 4 * x;
-        const bool cval = pair ? pt < A.pts : choff0 < A.c;        // this lane's 4 channels exist
-        const int choff = cval ? choff0 : 0;
-        auto row_addr = [&](int spec, int r) -> size_t {
-            if (spec) return ((size_t)bs[r] * A.pts + (size_t)pt * d2s[r] + (r - bs[r])) * A.c + choff;
-            return ((size_t)pt * A.na + r) * A.c + choff;
-        };
+        SB_DECODE_TASK(return);
         const unsigned cho = cval ? (unsigned)choff0 * 2u : SB_CHO_OOB, upt = (unsigned)pt;
         sbu32x2 raw[2][8];
 #pragma unroll
@@ -415,10 +449,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_bf16_kernel(SbArgs A)
                 }
         }
         f32x4 acc[4][4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        sb_zero(acc);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             sbf16x8 b[4];
@@ -443,21 +474,8 @@ __global__ __launch_bounds__(64 * SB_WAVES) void so3_basis_bf16_kernel(SbArgs A)
                 }
             }
         }
-        if constexpr (SMALL) {
-            if (A.dstat_x) sb_point_dstats<true>(acc, A, tab, rxs, upt, cho, pt, choff0, choff, cval, j);
-            else if (A.pstats) sb_point_stats<true>(acc, A.pstats, pt, A.c, choff0, cval, j);
-        } else if (A.pstats) sb_point_stats<true>(acc, A.pstats, pt, A.c, choff0, cval, j);
-        // acc[mt][nt][rr]: output row 16 mt + 4 j + rr, channel 4 x + nt
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int r = 16 * mt + 4 * j + rr;
-                const f32x4 v = {acc[mt][0][rr], acc[mt][1][rr], acc[mt][2][rr], acc[mt][3][rr]};
-                if constexpr (SMALL) sb_bst(out, rout, sb_off(tab.rbo, tab.rso, r, upt, cho), v);
-                else if (r < A.na && cval) sb_st(out + row_addr(A.out_spec, r), v);
-            }
-        if constexpr (SMALL) asm volatile("s_nop 4" ::: "memory");
+        SB_EPILOGUE_STATS(true);
+        SB_STORE_ROWS(__bf16);
     }
 }
 
@@ -492,10 +510,8 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
     __shared__ int bs[64], d2s[64];
     __shared__ SbTables tab;
     if constexpr (SMALL) sb_make_tables<4>(A, tab);
-    const unsigned nbytes = SMALL ? (unsigned)(A.pts * A.na * A.c * 4LL) : 0u;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(A.in), 0, (int)nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(A.out, 0, (int)nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rxs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(A.dstat_x ? A.dstat_x : A.in), 0, (int)nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = sb_rsrc<4, SMALL>(A, A.in), rout = sb_rsrc<4, SMALL>(A, A.out);
+    const __amdgpu_buffer_rsrc_t rxs = sb_rsrc<4, SMALL>(A, A.dstat_x ? A.dstat_x : A.in);
     for (int i = threadIdx.x; i < 64 * 64; i += blockDim.x) {
         const int r = i >> 6, q = i & 63;
         const float v = (r < A.na && q < A.na) ? A.M[r * A.na + q] : 0.0f;
@@ -506,35 +522,16 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
         Mp[1][r * SBH_LD + q] = mid;
         Mp[2][r * SBH_LD + q] = (__bf16)(r1 - (float)mid);
     }
-    if (threadIdx.x < 64) {
-        const int f = threadIdx.x < A.na ? threadIdx.x : 0;
-        bs[threadIdx.x] = A.blk[2 * f];
-        d2s[threadIdx.x] = A.blk[2 * f + 1];
-    }
+    sb_fill_blocks(A, bs, d2s);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int x = lane & 15, j = lane >> 4;
     const int ncb = (A.c + 63) >> 6;      // c % 32 == 0: the last block of a 32 (mod 64) width is half empty (lanes x >= 8)
     const float *in = static_cast<const float *>(A.in);
-    float *out = static_cast<float *>(A.out);
     float vmax = 0.0f;                    // max |output| of this lane's tasks (A.amax)
     for (int it = 0; it < SB_TPW; ++it) {
-        const long long task = ((long long)blockIdx.x * SB_WAVES + wave) * SB_TPW + it;
-        // c == 32 (the first two blocks of the rotation / 3DMatch networks): a 64-channel block would leave lanes x >= 8 idle
-        // (round 3: "half empty"); instead a task is TWO points, lanes x >= 8 carry the second one -- only the per-lane point
-        // index of the loads, stores and statistics changes, M is the same for every column
-        const bool pair = SMALL && A.pair;
-        if (task >= (pair ? (A.pts + 1) >> 1 : A.pts * ncb)) break;
-        const long long pt = pair ? 2 * task + (x >> 3) : task / ncb;
-        const int cb = pair ? 0 : (int)(task - pt * ncb);
-        const int choff0 = pair ? 4 * (x & 7) : 64 * cb + 4 * x;
-        const bool cval = pair ? pt < A.pts : choff0 < A.c;        // this lane's 4 channels exist
-        const int choff = cval ? choff0 : 0;
-        auto row_addr = [&](int spec, int r) -> size_t {
-            if (spec) return ((size_t)bs[r] * A.pts + (size_t)pt * d2s[r] + (r - bs[r])) * A.c + choff;
-            return ((size_t)pt * A.na + r) * A.c + choff;
-        };
+        SB_DECODE_TASK(break);
         const unsigned cho = cval ? (unsigned)choff0 * 4u : SB_CHO_OOB, upt = (unsigned)pt;
         f32x4 raw[2][8];          // row 32 ks + 8 j + e, channels 4x .. 4x+3
 #pragma unroll
@@ -558,10 +555,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
                     }
         }
         f32x4 acc[4][4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        sb_zero(acc);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             sbf16x8 bh[4], bm[4], bl[4];
@@ -589,50 +583,9 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
 #undef EPN_SB_TERM
             }
         }
-        if constexpr (SMALL) {
-            if (A.dstat_x) sb_point_dstats<false>(acc, A, tab, rxs, upt, cho, pt, choff0, choff, cval, j);
-            else if (A.pstats) sb_point_stats<false>(acc, A.pstats, pt, A.c, choff0, cval, j);
-        } else if (A.pstats) sb_point_stats<false>(acc, A.pstats, pt, A.c, choff0, cval, j);
-        // rows >= na hold zeros (M is zero padded).  Lanes without channels do NOT under norm on load: their zero rows went
-        // through sb_norm1 with the statistics of point 0, channels 0..3, so their accumulators hold leaky(norm(0)) * rowsum(M),
-        // which is never stored -- such a lane contributes nothing to the maximum (the select after the scan)
-        if (A.amax) {
-            float tmax = 0.0f;            // (fmaxf drops NaNs by itself)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt)
-                    tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, __builtin_fmaxf(__builtin_fabsf(acc[mt][nt][0]), __builtin_fabsf(acc[mt][nt][1]))),
-                                           __builtin_fmaxf(__builtin_fabsf(acc[mt][nt][2]), __builtin_fabsf(acc[mt][nt][3])));
-            // An infinite output is left OUT of the maximum, as absmax4 / split_rows2 leave non-finite elements out (advisor
-            // finding, round 5: clamped to FLT_MAX it became the scale, 2^-113, and every finite element of the buffer
-            // underflowed to zero in the consuming GEMMs; an fp32 GEMM poisons only the rows the element belongs to).  The
-            // masked rescan runs only in a wave that saw one.
-            if (__builtin_amdgcn_ballot_w64(tmax > 3.4028235e38f) != 0ull) {
-                tmax = 0.0f;
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) {
-                            const float v = __builtin_fabsf(acc[mt][nt][rr]);
-                            tmax = __builtin_fmaxf(tmax, v <= 3.4028235e38f ? v : 0.0f);
-                        }
-            }
-            vmax = cval ? __builtin_fmaxf(vmax, tmax) : vmax;
-        }
-        // acc[mt][nt][rr]: output row 16 mt + 4 j + rr, channel 4 x + nt
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int r = 16 * mt + 4 * j + rr;
-                const f32x4 v = {acc[mt][0][rr], acc[mt][1][rr], acc[mt][2][rr], acc[mt][3][rr]};
-                if constexpr (SMALL) sb_bst(out, rout, sb_off(tab.rbo, tab.rso, r, upt, cho), v);
-                else if (r < A.na && cval) sb_st(out + row_addr(A.out_spec, r), v);
-            }
-        if constexpr (SMALL) asm volatile("s_nop 4" ::: "memory");
+        SB_EPILOGUE_STATS(false);
+        if (A.amax) vmax = sb_amax_scan(acc, cval, vmax);
+        SB_STORE_ROWS(float);
     }
     if (A.amax) {                         // one atomic per wave, and only when it would raise the value seen
 #pragma unroll
@@ -641,6 +594,9 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
         if (lane == 0 && m > __builtin_nontemporal_load(A.amax)) atomicMax(A.amax, m);
     }
 }
+#undef SB_DECODE_TASK
+#undef SB_EPILOGUE_STATS
+#undef SB_STORE_ROWS
 
 // ---- the convolution weights in the block-diagonal basis:  What^rho[(j, c), (i, o)] = sum_k W[o, c, k] rho(g_k)[i, j]
 // (so3_fourier.py).  Every training step re-expresses the weights of every IntraSO3Conv; as torch glue that was a [cout*cin,
@@ -650,14 +606,18 @@ __global__ __launch_bounds__(64 * SB_WAVES) __attribute__((amdgpu_waves_per_eu(2
 // What^T[(i, o), (j, c)] (the Bt operand of the forward GEMM), thread index c-fastest so that both layouts are written
 // coalesced.  Flat buffers: block rho at offset base_rho * cin * cout.
 constexpr int SW_KN_MAX = 16, SW_NA_MAX = 64;
+// R and the block table into LDS (both kernels; the caller synchronises)
+__device__ __forceinline__ void sw_fill_tables(const float *R, const int32_t *blk, int kn, int na, float *Rs, int *bs, int *d2s) {
+    for (int i = threadIdx.x; i < na * kn; i += blockDim.x) Rs[(i / kn) * SW_KN_MAX + i % kn] = R[i];
+    if ((int)threadIdx.x < na) { bs[threadIdx.x] = blk[2 * threadIdx.x]; d2s[threadIdx.x] = blk[2 * threadIdx.x + 1]; }
+}
 template <bool TR, typename TO = float>      // TO = __bf16: the operand copies of a bf16 network (no cast / transpose-cast launches)
 __global__ __launch_bounds__(256) void spectral_weights_kernel(const float *__restrict__ W, const float *__restrict__ R,
                                                                const int32_t *__restrict__ blk, int cout, int cin, int kn,
                                                                int na, TO *__restrict__ out) {
     __shared__ float Rs[SW_NA_MAX * SW_KN_MAX];
     __shared__ int bs[SW_NA_MAX], d2s[SW_NA_MAX];
-    for (int i = threadIdx.x; i < na * kn; i += blockDim.x) Rs[(i / kn) * SW_KN_MAX + i % kn] = R[i];
-    if ((int)threadIdx.x < na) { bs[threadIdx.x] = blk[2 * threadIdx.x]; d2s[threadIdx.x] = blk[2 * threadIdx.x + 1]; }
+    sw_fill_tables(R, blk, kn, na, Rs, bs, d2s);
     __syncthreads();
     const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= (long long)cin * cout) return;
@@ -688,8 +648,7 @@ __global__ __launch_bounds__(256) void spectral_weights_bwd_kernel(const float *
                                                                    int na, float *__restrict__ gW) {
     __shared__ float Rs[SW_NA_MAX * SW_KN_MAX];
     __shared__ int bs[SW_NA_MAX], d2s[SW_NA_MAX];
-    for (int i = threadIdx.x; i < na * kn; i += blockDim.x) Rs[(i / kn) * SW_KN_MAX + i % kn] = R[i];
-    if ((int)threadIdx.x < na) { bs[threadIdx.x] = blk[2 * threadIdx.x]; d2s[threadIdx.x] = blk[2 * threadIdx.x + 1]; }
+    sw_fill_tables(R, blk, kn, na, Rs, bs, d2s);
     __syncthreads();
     // four lanes per (c, o) pair, each a quarter of the spectral rows, combined by two shuffles per weight
     const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -733,30 +692,30 @@ static int sw_check(const void *a, const void *R, const int32_t *blocks, int cou
     return 0;
 }
 
-extern "C" int epn_spectral_weights_f32(const float *W, const float *R, const int32_t *blocks, int cout, int cin, int kn,
-                                        int na, float *what, float *what_t, epn_stream_t stream) {
+// What (plain block layout) and / or What^T, whichever is asked for
+template <typename TO>
+static int spectral_weights_any(const float *W, const float *R, const int32_t *blocks, int cout, int cin, int kn, int na,
+                                TO *what, TO *what_t, epn_stream_t stream) {
     int rc = sw_check(W, R, blocks, cout, cin, kn, na);
     if (rc) return rc;
     if (!what && !what_t) return EPN_ENULL;
     const unsigned grid = (unsigned)(((long long)cin * cout + 255) / 256);
     const unsigned fy = grid >= 1024 ? 4 : (grid >= 256 ? 6 : 12);          // slices of the spectral rows
-    if (what) EPN_LAUNCH(spectral_weights_kernel<false>, dim3(grid, fy), dim3(256), 0, epn_stream(stream), W, R, blocks, cout, cin, kn, na, what);
-    if (what_t) EPN_LAUNCH(spectral_weights_kernel<true>, dim3(grid, fy), dim3(256), 0, epn_stream(stream), W, R, blocks, cout, cin, kn, na, what_t);
+    if (what) EPN_LAUNCH((spectral_weights_kernel<false, TO>), dim3(grid, fy), dim3(256), 0, epn_stream(stream), W, R, blocks, cout, cin, kn, na, what);
+    if (what_t) EPN_LAUNCH((spectral_weights_kernel<true, TO>), dim3(grid, fy), dim3(256), 0, epn_stream(stream), W, R, blocks, cout, cin, kn, na, what_t);
     EPN_CHECK_LAUNCH();
     return 0;
 }
 
+extern "C" int epn_spectral_weights_f32(const float *W, const float *R, const int32_t *blocks, int cout, int cin, int kn,
+                                        int na, float *what, float *what_t, epn_stream_t stream) {
+    return spectral_weights_any<float>(W, R, blocks, cout, cin, kn, na, what, what_t, stream);
+}
+
 extern "C" int epn_spectral_weights_bf16(const float *W, const float *R, const int32_t *blocks, int cout, int cin, int kn,
                                          int na, void *what, void *what_t, epn_stream_t stream) {
-    int rc = sw_check(W, R, blocks, cout, cin, kn, na);
-    if (rc) return rc;
-    if (!what && !what_t) return EPN_ENULL;
-    const unsigned grid = (unsigned)(((long long)cin * cout + 255) / 256);
-    const unsigned fy = grid >= 1024 ? 4 : (grid >= 256 ? 6 : 12);
-    if (what) EPN_LAUNCH((spectral_weights_kernel<false, __bf16>), dim3(grid, fy), dim3(256), 0, epn_stream(stream), W, R, blocks, cout, cin, kn, na, static_cast<__bf16 *>(what));
-    if (what_t) EPN_LAUNCH((spectral_weights_kernel<true, __bf16>), dim3(grid, fy), dim3(256), 0, epn_stream(stream), W, R, blocks, cout, cin, kn, na, static_cast<__bf16 *>(what_t));
-    EPN_CHECK_LAUNCH();
-    return 0;
+    return spectral_weights_any<__bf16>(W, R, blocks, cout, cin, kn, na, static_cast<__bf16 *>(what),
+                                        static_cast<__bf16 *>(what_t), stream);
 }
 
 extern "C" int epn_spectral_weights_bwd_f32(const float *grad_what, const float *R, const int32_t *blocks, int cout, int cin,
@@ -770,17 +729,25 @@ extern "C" int epn_spectral_weights_bwd_f32(const float *grad_what, const float 
     return 0;
 }
 
+// the norm of a norm-on-load / dstats call; default-constructed: none
 struct SbNormHost {
-    const float *sums, *gamma, *beta;
-    int groups;
-    long long pts_per_group;
-    float eps, slope;
+    bool on = false;
+    const float *sums = nullptr, *gamma = nullptr, *beta = nullptr;
+    int groups = 1;
+    long long pts_per_group = 0;
+    float eps = 0.f, slope = 0.f;
     bool frozen = false;      // sums is stats[c][2] = (mean, var), groups = 1 (epn_so3_basis_norm_frozen_*)
+    SbNormHost() = default;
+    SbNormHost(const float *sums_, int groups_, long long pts_per_group_, const float *gamma_, const float *beta_, float eps_,
+               float slope_, bool frozen_ = false)
+        : on(true), sums(sums_), gamma(gamma_), beta(beta_), groups(groups_), pts_per_group(pts_per_group_), eps(eps_),
+          slope(slope_), frozen(frozen_) {}
 };
 
+// family: 0 = fp32 MFMA, 1 = bf16 storage, 2 = fp32 storage in the split form
 static int so3_basis_any(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
-                        int in_spectral, int out_spectral, void *out, int bf16, epn_stream_t stream,
-                        const SbNormHost *nh = nullptr, float *point_stats = nullptr, const void *dstat_x = nullptr,
+                        int in_spectral, int out_spectral, void *out, int family, epn_stream_t stream,
+                        const SbNormHost &nh = SbNormHost(), float *point_stats = nullptr, const void *dstat_x = nullptr,
                         float *amax_out = nullptr) {
     if (pts < 0 || na < 4 || na > 64 || (na & 3) || c < 32 || (c & 31)) return EPN_EINVAL;
     if (pts == 0) return 0;
@@ -790,51 +757,39 @@ static int so3_basis_any(const void *in, const float *M, const int32_t *blocks, 
     A.in_spec = in_spectral; A.out_spec = out_spectral; A.dstat_x = dstat_x;
     A.amax = reinterpret_cast<unsigned *>(amax_out);
     if (amax_out) {
-        if (bf16 != 2) return EPN_EINVAL;       // the maximum is produced by the fp32 split-form kernel only
+        if (family != 2) return EPN_EINVAL;     // the maximum is produced by the fp32 split-form kernel only
         EPN_HIP(hipMemsetAsync(amax_out, 0, sizeof(float), epn_stream(stream)));
     }
     A.nsums = nullptr; A.ngamma = A.nbeta = nullptr; A.neps = 0.f; A.nslope = 0.f; A.ninv_rows = 0.f; A.ngroups = 1;
     A.npts_per_group = pts;
-    if (nh) {
-        if (!nh->sums) return EPN_ENULL;
-        if ((in_spectral && !dstat_x) || nh->groups < 1 || nh->pts_per_group < 1 || (nh->groups > 1 && nh->groups * nh->pts_per_group != pts))
+    if (nh.on) {
+        if (!nh.sums) return EPN_ENULL;
+        if ((in_spectral && !dstat_x) || nh.groups < 1 || nh.pts_per_group < 1 || (nh.groups > 1 && nh.groups * nh.pts_per_group != pts))
             return EPN_EINVAL;
-        A.nsums = nh->sums; A.ngamma = nh->gamma; A.nbeta = nh->beta; A.neps = nh->eps; A.nslope = nh->slope;
-        A.ngroups = nh->groups; A.npts_per_group = nh->groups > 1 ? nh->pts_per_group : pts;
+        A.nsums = nh.sums; A.ngamma = nh.gamma; A.nbeta = nh.beta; A.neps = nh.eps; A.nslope = nh.slope;
+        A.ngroups = nh.groups; A.npts_per_group = nh.groups > 1 ? nh.pts_per_group : pts;
         A.ninv_rows = 1.0f / ((float)A.npts_per_group * (float)na);
     }
-    const long long bytes_ = pts * na * c * (bf16 == 1 ? 2LL : 4LL);
-    A.pair = (c == 32 && bytes_ < 0x7fffff00LL && pts < (1LL << 24)) ? 1 : 0;
+    const bool fits32 = pts * na * c * (family == 1 ? 2LL : 4LL) < 0x7fffff00LL && pts < (1LL << 24);
+    A.pair = (c == 32 && fits32) ? 1 : 0;
     const long long tasks = A.pair ? (pts + 1) / 2 : pts * ((c + 63) >> 6);
     const long long per_wg = (long long)SB_WAVES * SB_TPW;
     const dim3 grid((unsigned)((tasks + per_wg - 1) / per_wg));
     // 32-bit row offsets + buffer instructions when the tensor is below 2 GiB and the per-point strides fit 24 bits
-    const long long bytes = pts * na * c * (bf16 == 1 ? 2LL : 4LL);
-    const bool small_t = bytes < 0x7fffff00LL && pts < (1LL << 24) && (long long)na * c * 4 < (1LL << 24);
+    const bool small_t = fits32 && (long long)na * c * 4 < (1LL << 24);
     // dstat_x exists in the 32-bit forms only: the 64-bit kernels would write plain (sum, sum of squares) into point_dstats
-    if (dstat_x && (!small_t || !point_stats || !nh || out_spectral)) return EPN_EINVAL;
-    if (nh && nh->frozen) {
-        if (dstat_x || point_stats || amax_out || nh->groups != 1) return EPN_EINVAL;
-        if (bf16 == 1) {
-            if (small_t) EPN_LAUNCH((so3_basis_bf16_kernel<true, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-            else EPN_LAUNCH((so3_basis_bf16_kernel<false, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-        } else if (bf16 == 2) {
-            if (small_t) EPN_LAUNCH((so3_basis_x3_kernel<true, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-            else EPN_LAUNCH((so3_basis_x3_kernel<false, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-        } else {
-            if (small_t) EPN_LAUNCH((so3_basis_kernel<float, true, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-            else EPN_LAUNCH((so3_basis_kernel<float, false, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-        }
-    } else if (bf16 == 1) {
-        if (small_t) EPN_LAUNCH(so3_basis_bf16_kernel<true>, grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-        else EPN_LAUNCH(so3_basis_bf16_kernel<false>, grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-    } else if (bf16 == 2) {                                                  // fp32, split form
-        if (small_t) EPN_LAUNCH(so3_basis_x3_kernel<true>, grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-        else EPN_LAUNCH(so3_basis_x3_kernel<false>, grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-    } else {
-        if (small_t) EPN_LAUNCH((so3_basis_kernel<float, true>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-        else EPN_LAUNCH((so3_basis_kernel<float, false>), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
-    }
+    if (dstat_x && (!small_t || !point_stats || !nh.on || out_spectral)) return EPN_EINVAL;
+    const bool frozen = nh.on && nh.frozen;
+    if (frozen && (dstat_x || point_stats || amax_out || nh.groups != 1)) return EPN_EINVAL;
+    static void (*const kernels[3][2][2])(SbArgs) = {       // [family][small_t][frozen]
+        {{so3_basis_kernel<float, false>, so3_basis_kernel<float, false, true>},
+         {so3_basis_kernel<float, true>, so3_basis_kernel<float, true, true>}},
+        {{so3_basis_bf16_kernel<false>, so3_basis_bf16_kernel<false, true>},
+         {so3_basis_bf16_kernel<true>, so3_basis_bf16_kernel<true, true>}},
+        {{so3_basis_x3_kernel<false>, so3_basis_x3_kernel<false, true>},
+         {so3_basis_x3_kernel<true>, so3_basis_x3_kernel<true, true>}},
+    };
+    EPN_LAUNCH((*kernels[family == 1 ? 1 : (family == 2 ? 2 : 0)][small_t][frozen]), grid, dim3(64 * SB_WAVES), 0, epn_stream(stream), A);
     EPN_CHECK_LAUNCH();
     return 0;
 }
@@ -851,15 +806,15 @@ extern "C" int epn_so3_basis_split_f32(const float *in, const float *M, const in
 extern "C" int epn_so3_basis_amax_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                             int in_spectral, int out_spectral, float *out, float *amax_out, epn_stream_t stream) {
     if (!amax_out) return EPN_ENULL;
-    return so3_basis_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, 2, stream, nullptr, nullptr, nullptr, amax_out);
+    return so3_basis_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, 2, stream, SbNormHost(), nullptr, nullptr, amax_out);
 }
 extern "C" int epn_so3_basis_norm_amax_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na,
                                                  int c, int out_spectral, float *out, const float *sums, int groups,
                                                  long long pts_per_group, const float *gamma, const float *beta, float eps,
                                                  float slope, float *amax_out, epn_stream_t stream) {
     if (!amax_out) return EPN_ENULL;
-    const SbNormHost nh = {sums, gamma, beta, groups, pts_per_group, eps, slope};
-    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 2, stream, &nh, nullptr, nullptr, amax_out);
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 2, stream,
+                         SbNormHost(sums, groups, pts_per_group, gamma, beta, eps, slope), nullptr, nullptr, amax_out);
 }
 extern "C" int epn_so3_basis_bf16(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                   int in_spectral, int out_spectral, void *out, epn_stream_t stream) {
@@ -867,24 +822,24 @@ extern "C" int epn_so3_basis_bf16(const void *in, const float *M, const int32_t 
 }
 
 // the change of basis + per-point block partials of the output's per-channel statistics (see SbArgs::pstats)
-extern "C" int epn_so3_basis_stats_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
-                                       int in_spectral, int out_spectral, float *out, float *point_stats, epn_stream_t stream) {
+static int so3_basis_stats_any(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
+                               int in_spectral, int out_spectral, void *out, float *point_stats, int family, epn_stream_t stream) {
     if (!point_stats) return EPN_ENULL;
     if (out_spectral) return EPN_EINVAL;      // statistics over the ANCHOR rows of a point: plain output layout only
-    return so3_basis_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, 0, stream, nullptr, point_stats);
+    return so3_basis_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, family, stream, SbNormHost(), point_stats);
+}
+extern "C" int epn_so3_basis_stats_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
+                                       int in_spectral, int out_spectral, float *out, float *point_stats, epn_stream_t stream) {
+    return so3_basis_stats_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, point_stats, 0, stream);
 }
 extern "C" int epn_so3_basis_stats_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na,
                                              int c, int in_spectral, int out_spectral, float *out, float *point_stats,
                                              epn_stream_t stream) {
-    if (!point_stats) return EPN_ENULL;
-    if (out_spectral) return EPN_EINVAL;      // statistics over the ANCHOR rows of a point: plain output layout only
-    return so3_basis_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, 2, stream, nullptr, point_stats);
+    return so3_basis_stats_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, point_stats, 2, stream);
 }
 extern "C" int epn_so3_basis_stats_bf16(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                         int in_spectral, int out_spectral, void *out, float *point_stats, epn_stream_t stream) {
-    if (!point_stats) return EPN_ENULL;
-    if (out_spectral) return EPN_EINVAL;      // statistics over the ANCHOR rows of a point: plain output layout only
-    return so3_basis_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, 1, stream, nullptr, point_stats);
+    return so3_basis_stats_any(in, M, blocks, pts, na, c, in_spectral, out_spectral, out, point_stats, 1, stream);
 }
 
 // Inverse transform of a spectral GRADIENT + the block partials of the backward reduction of the norm that preceded the
@@ -893,32 +848,27 @@ extern "C" int epn_so3_basis_stats_bf16(const void *in, const float *M, const in
 // Shapes the 32-bit-offset kernels do not take (2 GiB or more, or na * c * 4 >= 2^24): EPN_EINVAL (use epn_so3_basis_* +
 // epn_norm_act_bwd_reduce_*).
 static int so3_basis_dstats_any(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c, void *out,
-                                const void *x_cl, const float *sums, int groups, long long pts_per_group, const float *gamma,
-                                const float *beta, float eps, float slope, float *point_dstats, int bf16, epn_stream_t stream) {
+                                const void *x_cl, const SbNormHost &nh, float *point_dstats, int family, epn_stream_t stream) {
     if (!x_cl || !point_dstats) return EPN_ENULL;
-    const SbNormHost nh = {sums, gamma, beta, groups, pts_per_group, eps, slope};
-    return so3_basis_any(in, M, blocks, pts, na, c, 1, 0, out, bf16, stream, &nh, point_dstats, x_cl);
+    return so3_basis_any(in, M, blocks, pts, na, c, 1, 0, out, family, stream, nh, point_dstats, x_cl);
 }
 extern "C" int epn_so3_basis_dstats_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                         float *out, const float *x_cl, const float *sums, int groups, long long pts_per_group,
                                         const float *gamma, const float *beta, float eps, float slope, float *point_dstats,
                                         epn_stream_t stream) {
-    return so3_basis_dstats_any(in, M, blocks, pts, na, c, out, x_cl, sums, groups, pts_per_group, gamma, beta, eps, slope,
-                                point_dstats, 0, stream);
+    return so3_basis_dstats_any(in, M, blocks, pts, na, c, out, x_cl, SbNormHost(sums, groups, pts_per_group, gamma, beta, eps, slope), point_dstats, 0, stream);
 }
 extern "C" int epn_so3_basis_dstats_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na,
                                               int c, float *out, const float *x_cl, const float *sums, int groups,
                                               long long pts_per_group, const float *gamma, const float *beta, float eps,
                                               float slope, float *point_dstats, epn_stream_t stream) {
-    return so3_basis_dstats_any(in, M, blocks, pts, na, c, out, x_cl, sums, groups, pts_per_group, gamma, beta, eps, slope,
-                                point_dstats, 2, stream);
+    return so3_basis_dstats_any(in, M, blocks, pts, na, c, out, x_cl, SbNormHost(sums, groups, pts_per_group, gamma, beta, eps, slope), point_dstats, 2, stream);
 }
 extern "C" int epn_so3_basis_dstats_bf16(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                          void *out, const void *x_cl, const float *sums, int groups, long long pts_per_group,
                                          const float *gamma, const float *beta, float eps, float slope, float *point_dstats,
                                          epn_stream_t stream) {
-    return so3_basis_dstats_any(in, M, blocks, pts, na, c, out, x_cl, sums, groups, pts_per_group, gamma, beta, eps, slope,
-                                point_dstats, 1, stream);
+    return so3_basis_dstats_any(in, M, blocks, pts, na, c, out, x_cl, SbNormHost(sums, groups, pts_per_group, gamma, beta, eps, slope), point_dstats, 1, stream);
 }
 
 // leaky_relu(norm(in)) applied on load, then the change of basis (in plain layout only): sums[g][c] = (sum x, sum x^2)
@@ -926,39 +876,33 @@ extern "C" int epn_so3_basis_dstats_bf16(const void *in, const float *M, const i
 extern "C" int epn_so3_basis_norm_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                       int out_spectral, float *out, const float *sums, int groups, long long pts_per_group,
                                       const float *gamma, const float *beta, float eps, float slope, epn_stream_t stream) {
-    const SbNormHost nh = {sums, gamma, beta, groups, pts_per_group, eps, slope};
-    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 0, stream, &nh);
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 0, stream, SbNormHost(sums, groups, pts_per_group, gamma, beta, eps, slope));
 }
 extern "C" int epn_so3_basis_norm_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na,
                                             int c, int out_spectral, float *out, const float *sums, int groups,
                                             long long pts_per_group, const float *gamma, const float *beta, float eps,
                                             float slope, epn_stream_t stream) {
-    const SbNormHost nh = {sums, gamma, beta, groups, pts_per_group, eps, slope};
-    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 2, stream, &nh);
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 2, stream, SbNormHost(sums, groups, pts_per_group, gamma, beta, eps, slope));
 }
 extern "C" int epn_so3_basis_norm_bf16(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                        int out_spectral, void *out, const float *sums, int groups, long long pts_per_group,
                                        const float *gamma, const float *beta, float eps, float slope, epn_stream_t stream) {
-    const SbNormHost nh = {sums, gamma, beta, groups, pts_per_group, eps, slope};
-    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 1, stream, &nh);
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 1, stream, SbNormHost(sums, groups, pts_per_group, gamma, beta, eps, slope));
 }
 
 // The same with FROZEN statistics: stats[c][2] = (mean, var) of an eval-mode BatchNorm2d (epn_bn_frozen_stats_f32), one group
 extern "C" int epn_so3_basis_norm_frozen_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                              int out_spectral, float *out, const float *stats, const float *gamma,
                                              const float *beta, float eps, float slope, epn_stream_t stream) {
-    const SbNormHost nh = {stats, gamma, beta, 1, pts, eps, slope, true};
-    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 0, stream, &nh);
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 0, stream, SbNormHost(stats, 1, pts, gamma, beta, eps, slope, true));
 }
 extern "C" int epn_so3_basis_norm_frozen_split_f32(const float *in, const float *M, const int32_t *blocks, long long pts, int na,
                                                    int c, int out_spectral, float *out, const float *stats, const float *gamma,
                                                    const float *beta, float eps, float slope, epn_stream_t stream) {
-    const SbNormHost nh = {stats, gamma, beta, 1, pts, eps, slope, true};
-    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 2, stream, &nh);
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 2, stream, SbNormHost(stats, 1, pts, gamma, beta, eps, slope, true));
 }
 extern "C" int epn_so3_basis_norm_frozen_bf16(const void *in, const float *M, const int32_t *blocks, long long pts, int na, int c,
                                               int out_spectral, void *out, const float *stats, const float *gamma,
                                               const float *beta, float eps, float slope, epn_stream_t stream) {
-    const SbNormHost nh = {stats, gamma, beta, 1, pts, eps, slope, true};
-    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 1, stream, &nh);
+    return so3_basis_any(in, M, blocks, pts, na, c, 0, out_spectral, out, 1, stream, SbNormHost(stats, 1, pts, gamma, beta, eps, slope, true));
 }
