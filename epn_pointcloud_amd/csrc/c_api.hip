@@ -170,9 +170,9 @@ extern "C" int epn_inter_so3conv_fwd_f32(const epn_inter_desc *d, const float *f
     if (!feats_cl || !W || !out_cl) return EPN_ENULL;
     if (d->b == 0 || d->p2 == 0) return 0;
     if (mf) {
-        rc = launch_inter_tables_mfma(d, base + ws.rk_off, base + ws.rk4_off, base + ws.beta_off, st);
+        rc = launch_inter_tables_mfma(d, base + ws.rk4_off, st);
         if (rc) return rc;
-        return launch_inter_fwd_mfma(d, base + ws.rk4_off, base + ws.beta_off, feats_cl, W, out_cl, st);
+        return launch_inter_fwd_mfma(d, base + ws.rk4_off, feats_cl, W, out_cl, st);
     }
     if (inter_c1_fwd_ok(d) && !force_generic())
         return launch_inter_c1_fwd(d, base + ws.rk_off, feats_cl, W, out_cl, st, nullptr,
@@ -225,7 +225,7 @@ extern "C" int epn_inter_so3conv_bwd_data_f32(const epn_inter_desc *d, const flo
     if (d->b == 0 || d->p2 == 0) return 0;
     if (!grad_out_cl || !W) return EPN_ENULL;
     if (mf) {
-        rc = launch_inter_tables_mfma(d, base + ws.rk_off, base + ws.rk4_off, base + ws.beta_off, st);
+        rc = launch_inter_tables_mfma(d, base + ws.rk4_off, st);
         if (rc) return rc;
         return launch_inter_bwd_data_mfma(d, base + ws.rk4_off, base + ws.big_off, grad_out_cl, W, grad_feats_cl, st);
     }
@@ -249,10 +249,9 @@ extern "C" int epn_inter_so3conv_bwd_weight_f32(const epn_inter_desc *d, const f
     if (d->b == 0 || d->p2 == 0) return 0;
     if (!feats_cl || !grad_out_cl) return EPN_ENULL;
     if (mf) {
-        rc = launch_inter_tables_mfma(d, base + ws.rk_off, base + ws.rk4_off, base + ws.beta_off, st);
+        rc = launch_inter_tables_mfma(d, base + ws.rk4_off, st);
         if (rc) return rc;
-        return launch_inter_bwd_weight_mfma(d, base + ws.rk4_off, base + ws.beta_off, feats_cl, grad_out_cl, grad_W,
-                                            st);
+        return launch_inter_bwd_weight_mfma(d, base + ws.rk4_off, feats_cl, grad_out_cl, grad_W, st);
     }
     if (inter_c1_bwd_weight_ok(d) && !force_generic())
         return launch_inter_c1_bwd_weight(d, base + ws.rk_off, feats_cl, grad_out_cl, grad_W, st);
@@ -304,7 +303,7 @@ static int inter_onchip_fwd(const epn_inter_desc *d, const void *feats_cl, const
     if (rc) return rc;
     if (d->b == 0 || d->p2 == 0) return 0;
     if (!feats_cl || !W || !out_cl) return EPN_ENULL;
-    rc = launch_inter_tables_mfma(d, base + ws.rk_off, base + ws.rk4_off, base + ws.beta_off, st);
+    rc = launch_inter_tables_mfma(d, base + ws.rk4_off, st);
     if (rc) return rc;
     return launch_inter_fx_fwd(d, base + ws.rk4_off, feats_cl, W, out_cl, base + ws.big_off, bf16, st);
 }
@@ -329,7 +328,7 @@ static int inter_group_any(const epn_inter_desc *d, const void *feats_cl, void *
     if (d->b == 0 || d->p2 == 0) return 0;
     if (!feats_cl || !grouped) return EPN_ENULL;
     if (inter_group_mfma_ok(d) && !force_generic()) {
-        rc = launch_inter_tables_mfma(d, base + ws.rk_off, base + ws.rk4_off, base + ws.beta_off, st);
+        rc = launch_inter_tables_mfma(d, base + ws.rk4_off, st);
         if (rc) return rc;
         return launch_inter_group_mfma(d, base + ws.rk4_off, feats_cl, grouped, bf16, st, packed);
     }
@@ -350,7 +349,7 @@ static int inter_ungroup_any(const epn_inter_desc *d, const void *grad_grouped, 
     if (d->b == 0 || d->p2 == 0) return 0;
     if (!grad_grouped) return EPN_ENULL;
     if (inter_group_mfma_ok(d) && !force_generic()) {
-        rc = launch_inter_tables_mfma(d, base + ws.rk_off, base + ws.rk4_off, base + ws.beta_off, st);
+        rc = launch_inter_tables_mfma(d, base + ws.rk4_off, st);
         if (rc) return rc;
         return launch_inter_ungroup_mfma(d, base + ws.rk4_off, grad_grouped, grad_feats_cl,
                                          reinterpret_cast<int32_t *>(base + ws.order_off), bf16, st);
@@ -454,7 +453,7 @@ static int inter_ungroup_cloud_any(const epn_inter_desc *d, const void *grad_gro
     }
     if (!grad_grouped) return EPN_ENULL;
     float *base = static_cast<float *>(workspace);
-    rc = launch_inter_tables_mfma(d, base + ws.rk_off, base + ws.rk4_off, base + ws.beta_off, st);
+    rc = launch_inter_tables_mfma(d, base + ws.rk4_off, st);
     if (rc) return rc;
     return launch_inter_ungroup_cloud(d, base + ws.rk4_off, grad_grouped, dg_amax, grad_feats_cl, add, bf16, out_bf16, base + ws.big_off, st);
 }
@@ -520,7 +519,7 @@ static int inter_ungroup_det_any(const epn_inter_desc *d, const void *grad_group
     if (!grad_grouped || !offsets || !entries || !slab) return EPN_ENULL;
     const size_t need = (size_t)d->b * d->p2 * d->nn * d->na * d->cin * (bf16 ? 2 : 4);
     if (slab_bytes < need) return EPN_EWORKSPACE;
-    rc = launch_inter_tables_mfma(d, base + ws.rk_off, base + ws.rk4_off, base + ws.beta_off, st);
+    rc = launch_inter_tables_mfma(d, base + ws.rk4_off, st);
     if (rc) return rc;
     // room behind the slab for one byte per (point, neighbour slot): the pre-reduced form (a third of the slab traffic)
     const size_t flags = (size_t)d->b * d->p2 * d->nn;

@@ -57,13 +57,13 @@ int launch_inter_c1_bwd_weight(const epn_inter_desc *d, const float *rk, const f
                                float *dW, hipStream_t st, const float *grouped_saved = nullptr);
 
 // inter_mfma.hip / intra_mfma.hip (fused MFMA kernels; cin, cout multiples of 16)
-int launch_inter_tables_mfma(const epn_inter_desc *d, const float *rk, float *rk4, float *beta, hipStream_t st);
-int launch_inter_fwd_mfma(const epn_inter_desc *d, const float *rk4, const float *beta, const float *feats,
-                          const float *W, float *out, hipStream_t st);
-int launch_inter_bwd_data_mfma(const epn_inter_desc *d, const float *rk4, const float *wt_scratch, const float *dOut,
+int launch_inter_tables_mfma(const epn_inter_desc *d, float *rk4, hipStream_t st);
+int launch_inter_fwd_mfma(const epn_inter_desc *d, const float *rk4, const float *feats, const float *W, float *out,
+                          hipStream_t st);
+int launch_inter_bwd_data_mfma(const epn_inter_desc *d, const float *rk4, float *wt_scratch, const float *dOut,
                                const float *W, float *dF, hipStream_t st);
-int launch_inter_bwd_weight_mfma(const epn_inter_desc *d, const float *rk4, const float *beta, const float *feats,
-                                 const float *dOut, float *dW, hipStream_t st);
+int launch_inter_bwd_weight_mfma(const epn_inter_desc *d, const float *rk4, const float *feats, const float *dOut,
+                                 float *dW, hipStream_t st);
 // grouping only ("split" path: the weight contraction is left to the BLAS library); any cout
 static inline bool inter_group_mfma_ok(const epn_inter_desc *d) {
     return inter_mfma_available() && !d->dense_w && d->cin % 16 == 0 && d->ks <= EPN_KS_MAX && d->ks % 4 == 0 &&

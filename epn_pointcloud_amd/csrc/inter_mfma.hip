@@ -820,11 +820,7 @@ __global__ __launch_bounds__(64 * NW) void inter_group_kernel(InterArgs A) {
 #define EPN_G_STORE_AUX 2     // cache policy of the stores of G (gfx940+: bit 0 = sc0, bit 1 = nt, bit 4 = sc1)
 #endif
 template <int NT, int KT, typename TF, int CG>
-#ifdef EPN_GRP_NO_WPE
-__global__ __launch_bounds__(64 * NW)
-#else
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NT <= 4 ? 2 : 1)))
-#endif
 void inter_group_wide_kernel(InterArgs A) {
     constexpr bool BF = sizeof(TF) == 2;
     typedef unsigned uvec __attribute__((ext_vector_type(BF ? CG / 2 : CG)));   // one lane's CG channels of one row
@@ -898,10 +894,6 @@ void inter_group_wide_kernel(InterArgs A) {
             }
         };
         auto store_g = [&](unsigned voff, unsigned soff, f32x4 g) {
-#ifdef EPN_GRP_FLAT_ST
-            if (voff != 0x80000000u) st4f(reinterpret_cast<TF *>(reinterpret_cast<char *>(G) + soff + voff), g);
-            return;
-#endif
             // The whole offset goes into the VGPR offset, the scalar offset stays the literal 0.  With the row offset in an
             // SGPR (`buffer_store_dwordx4 v[66:69], v59, s[4:7], s52 offen`) hipcc assumes the hardware interlocks a later
             // write of the data registers (GCNHazardRecognizer: "this hazard only exists if the instruction is not using a
@@ -1180,10 +1172,7 @@ __global__ __launch_bounds__(64 * GP) void inter_ungroup_shared_kernel(InterArgs
     // and readers agree: with bits 2 and 3 of the row swapped the two lane groups of a store are 8 rows = 272 = 16 banks apart
     // (disjoint), at the same 78 KB.  The readers' slot words (pk[], and list[] for destinations with more than three slots)
     // carry the permuted row.
-#ifndef EPN_UNG_ROWPERM
-#define EPN_UNG_ROWPERM 1
-#endif
-    constexpr bool RP = EPN_UNG_ROWPERM && CW == 2 && !DET;
+    constexpr bool RP = CW == 2 && !DET;
     auto rowp = [](unsigned e) -> unsigned { return RP ? ((e & ~12u) | ((e & 4u) << 1) | ((e & 8u) >> 1)) : e; };
     typedef typename std::conditional<CW == 2, short, int>::type ix_t;   // destinations < 32768 (p1 <= USH_TAB), slots < 1024
     static_assert((CW == 1 && CS == 1) || !DET, "the deterministic form handles one chunk per step");
@@ -1448,11 +1437,7 @@ __global__ __launch_bounds__(64 * GP) void inter_ungroup_shared_kernel(InterArgs
 // (round 6, measured: an LDS-only barrier here -- no wait for the previous step's atomics or the prefetched dG fragments --
 // changes nothing on the bf16 networks and costs the classification step 1.2 %: 530.6 / 529.0 against 536.6 / 536.5
 // point-clouds/s, A/B of two builds on one box, profiles/r06_ab_rawbar_onchip.txt.  The wait is not what the waves wait for.)
-#ifndef EPN_UNG_RAWBAR
-#define EPN_UNG_RAWBAR 0
-#endif
-            if constexpr (EPN_UNG_RAWBAR) lds_barrier();     // (inter_device.h: no wait for the atomics / the prefetched dG)
-            else __syncthreads();
+            __syncthreads();
             const float *rb = Tb + (ph & (NB - 1)) * BS;
             float *dstep = dcloud + (size_t)a * A.cin + 16 * cs * CW;      // wave-uniform
 #ifdef EPN_TUNING
@@ -1478,10 +1463,7 @@ __global__ __launch_bounds__(64 * GP) void inter_ungroup_shared_kernel(InterArgs
                     atomicAdd(dstep + ((unsigned)cnt[u] + (unsigned)c), sum);
                 }
             }
-            if constexpr (NB == 1) {
-                if constexpr (EPN_UNG_RAWBAR) lds_barrier();
-                else __syncthreads();
-            }
+            if constexpr (NB == 1) __syncthreads();
         }
     }
     }
@@ -1700,33 +1682,93 @@ InterArgs make_args(const epn_inter_desc *d, const float *rk4) {
 
 size_t gs_bytes(const epn_inter_desc *d) { return (size_t)NW * 16 * (16 * d->ks + 4) * sizeof(float); }
 
-template <typename K>
-int set_lds(K kern, size_t bytes) {
-    EPN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bytes));
+// ------------------------------------------------------------------------------------------------ the kernel instances
+// Every instance the launchers below start is named ONCE, here, in a table indexed by the key its launcher computes.  A
+// launcher looks the host stub up (that pointer is what EPN_LAUNCH records for epn_last_kernel), refuses with EPN_EINVAL
+// when the table has none, and goes through launch_inter().
+typedef void (*InterKernel)(InterArgs);
+typedef void (*InterScatterKernel)(InterArgs, const int32_t *, unsigned char *);
+
+// [nt_slot][kt_slot] of a kernel template whose first arguments are <NT, KT> and whose further ones follow
+#define EPN_NT_KT(K, ...)                                                                                  \
+    {{K<1, 1, __VA_ARGS__>, K<1, 2, __VA_ARGS__>}, {K<2, 1, __VA_ARGS__>, K<2, 2, __VA_ARGS__>},          \
+     {K<4, 1, __VA_ARGS__>, K<4, 2, __VA_ARGS__>}, {K<8, 1, __VA_ARGS__>, K<8, 2, __VA_ARGS__>}}
+// NT = 1, 2, 4, 8 neighbour tiles of 16 (the smallest that holds nn) and KT = 1, 2 kernel-point tiles
+int nt_slot(const epn_inter_desc *d) {
+    const int nt = (d->nn + 15) / 16;
+    return nt <= 1 ? 0 : (nt <= 2 ? 1 : (nt <= 4 ? 2 : 3));
+}
+int kt_slot(const epn_inter_desc *d) { return (d->ks + 15) / 16 == 1 ? 0 : 1; }
+
+// the fused passes: 4-wave kernels [nt_slot][kt_slot], 8-wave kernels [nn > 16][...]
+const InterKernel fwd_kernels[4][2] = {{inter_fwd_kernel<1, 1>, inter_fwd_kernel<1, 2>}, {inter_fwd_kernel<2, 1>, inter_fwd_kernel<2, 2>},
+                                       {inter_fwd_kernel<4, 1>, inter_fwd_kernel<4, 2>}, {inter_fwd_kernel<8, 1>, inter_fwd_kernel<8, 2>}};
+const InterKernel fwd8_kernels[2][5] = {       // [nn > 16][mt_slot]: MT = cout / 16 = 1, 2, 4, 8, 16
+    {inter_fwd8_kernel<1, 1>, inter_fwd8_kernel<1, 2>, inter_fwd8_kernel<1, 4>, inter_fwd8_kernel<1, 8>, inter_fwd8_kernel<1, 16>},
+    {inter_fwd8_kernel<2, 1>, inter_fwd8_kernel<2, 2>, inter_fwd8_kernel<2, 4>, inter_fwd8_kernel<2, 8>, inter_fwd8_kernel<2, 16>}};
+int mt_slot(int mt) { return mt == 1 ? 0 : (mt == 2 ? 1 : (mt == 4 ? 2 : (mt == 8 ? 3 : (mt == 16 ? 4 : -1)))); }
+const InterKernel bwd_data_kernels[4][2] = EPN_NT_KT(inter_bwd_data_kernel, false);
+const InterKernel bwd_data_tight_kernels[4] = {          // [nt_slot]; ks = 32: unpadded tiles, KT = 2
+    inter_bwd_data_kernel<1, 2, true>, inter_bwd_data_kernel<2, 2, true>, inter_bwd_data_kernel<4, 2, true>, inter_bwd_data_kernel<8, 2, true>};
+const InterKernel bwd_data8_kernels[2][3] = {  // [nn > 16][ks = 16, 24, 32]: MH = ks / 2
+    {inter_bwd_data8_kernel<1, 1, 8>, inter_bwd_data8_kernel<1, 2, 12>, inter_bwd_data8_kernel<1, 2, 16>},
+    {inter_bwd_data8_kernel<2, 1, 8>, inter_bwd_data8_kernel<2, 2, 12>, inter_bwd_data8_kernel<2, 2, 16>}};
+const InterKernel bwd_weight_kernels[4][2] = {{inter_bwd_weight_kernel<1, 1>, inter_bwd_weight_kernel<1, 2>}, {inter_bwd_weight_kernel<2, 1>, inter_bwd_weight_kernel<2, 2>},
+                                              {inter_bwd_weight_kernel<4, 1>, inter_bwd_weight_kernel<4, 2>}, {inter_bwd_weight_kernel<8, 1>, inter_bwd_weight_kernel<8, 2>}};
+const InterKernel bwd_weight8_kernels[2][3] = {          // [nn > 16][MO = 2, 4, 8]
+    {inter_bwd_weight8_kernel<1, 2>, inter_bwd_weight8_kernel<1, 4>, inter_bwd_weight8_kernel<1, 8>},
+    {inter_bwd_weight8_kernel<2, 2>, inter_bwd_weight8_kernel<2, 4>, inter_bwd_weight8_kernel<2, 8>}};
+
+// grouping and its transposes: [bf16][nt_slot][kt_slot]; the wide grouping [bf16][CG == 4][nt_slot][kt_slot] (its launcher
+// asks for nn <= 64 only: the NT = 8 column is never looked up)
+const InterKernel group_kernels[2][4][2] = {EPN_NT_KT(inter_group_kernel, float), EPN_NT_KT(inter_group_kernel, __bf16)};
+const InterKernel group_wide_kernels[2][2][4][2] = {
+    {EPN_NT_KT(inter_group_wide_kernel, float, 2), EPN_NT_KT(inter_group_wide_kernel, float, 4)},
+    {EPN_NT_KT(inter_group_wide_kernel, __bf16, 2), EPN_NT_KT(inter_group_wide_kernel, __bf16, 4)}};
+const InterKernel ungroup_kernels[2][4][2] = {EPN_NT_KT(inter_ungroup_kernel, float), EPN_NT_KT(inter_ungroup_kernel, __bf16)};
+const InterKernel ungroup_slots_kernels[2][4][2] = {EPN_NT_KT(inter_ungroup_slots_kernel, float),
+                                                    EPN_NT_KT(inter_ungroup_slots_kernel, __bf16)};
+
+// The LDS-reduced scatter, [bf16][form][scatter_slot][kt_slot].  form: 0 = deterministic (DET: stores to the slab), 1 / 2 / 3 =
+// atomic with CW = 1 / 2 / 4 chunks per anchor step (CS = 1 throughout).  scatter_slot: the (NT, GP) pairs ungroup_group_points
+// can name.  NB = 2 tile buffers for the 8-point group of K <= 16, one for every other.  {}: no such instance -- CW = 4 holds
+// K <= 32 only, CW = 2 the 8-point groups of K = 32 / 64 (and <2, *, *, 16>, which the gp = 8 override keeps from being asked for).
+#define EPN_SCATTER(NT, GP, TG, ...)                                                                       \
+    {inter_ungroup_shared_kernel<NT, 1, TG, GP, ((NT == 1 && GP == 8) ? 2 : 1), __VA_ARGS__>,               \
+     inter_ungroup_shared_kernel<NT, 2, TG, GP, ((NT == 1 && GP == 8) ? 2 : 1), __VA_ARGS__>}
+#define EPN_SCATTER_ALL(TG, ...)                                                                           \
+    {EPN_SCATTER(1, 8, TG, __VA_ARGS__), EPN_SCATTER(2, 16, TG, __VA_ARGS__), EPN_SCATTER(2, 8, TG, __VA_ARGS__), \
+     EPN_SCATTER(4, 8, TG, __VA_ARGS__), EPN_SCATTER(4, 4, TG, __VA_ARGS__), EPN_SCATTER(8, 2, TG, __VA_ARGS__)}
+#define EPN_SCATTER_FORMS(TG)                                                                              \
+    {EPN_SCATTER_ALL(TG, true, 1, 1), EPN_SCATTER_ALL(TG, false, 1, 1),                                    \
+     {{}, EPN_SCATTER(2, 16, TG, false, 2, 1), EPN_SCATTER(2, 8, TG, false, 2, 1), EPN_SCATTER(4, 8, TG, false, 2, 1), {}, {}}, \
+     {EPN_SCATTER(1, 8, TG, false, 4, 1), EPN_SCATTER(2, 16, TG, false, 4, 1), EPN_SCATTER(2, 8, TG, false, 4, 1), {}, {}, {}}}
+const InterScatterKernel scatter_kernels[2][4][6][2] = {EPN_SCATTER_FORMS(float), EPN_SCATTER_FORMS(__bf16)};
+#undef EPN_SCATTER_FORMS
+#undef EPN_SCATTER_ALL
+#undef EPN_SCATTER
+#undef EPN_NT_KT
+// one lookup for both launchers of the scatter; nullptr: (NT, GP) is no pair of the table, or the form has no such instance
+InterScatterKernel scatter_kernel(const epn_inter_desc *d, int bf16, int form, int gp) {
+    static const int pairs[6][2] = {{0, 8}, {1, 16}, {1, 8}, {2, 8}, {2, 4}, {3, 2}};       // (nt_slot, GP) of scatter_slot
+    for (int s = 0; s < 6; ++s)
+        if (pairs[s][0] == nt_slot(d) && pairs[s][1] == gp) return scatter_kernels[bf16 ? 1 : 0][form][s][kt_slot(d)];
+    return nullptr;
+}
+
+// the launch path of every table above but the scatter's: raise the dynamic-LDS limit (lds = 0: the family has none), launch
+int launch_inter(InterKernel kern, dim3 grid, unsigned threads, size_t lds, hipStream_t st, const InterArgs &A) {
+    if (!kern) return EPN_EINVAL;
+    if (lds)
+        EPN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    EPN_LAUNCH((*kern), grid, dim3(threads), lds, st, A);
+    EPN_CHECK_LAUNCH();
     return 0;
 }
 
-#define EPN_DISPATCH_NT_KT(FN, ...)                                              \
-    do {                                                                         \
-        const int nt_ = (d->nn + 15) / 16, kt_ = (d->ks + 15) / 16;              \
-        if (kt_ == 1) {                                                          \
-            if (nt_ <= 1) FN(1, 1, __VA_ARGS__);                                 \
-            else if (nt_ <= 2) FN(2, 1, __VA_ARGS__);                            \
-            else if (nt_ <= 4) FN(4, 1, __VA_ARGS__);                            \
-            else FN(8, 1, __VA_ARGS__);                                          \
-        } else {                                                                 \
-            if (nt_ <= 1) FN(1, 2, __VA_ARGS__);                                 \
-            else if (nt_ <= 2) FN(2, 2, __VA_ARGS__);                            \
-            else if (nt_ <= 4) FN(4, 2, __VA_ARGS__);                            \
-            else FN(8, 2, __VA_ARGS__);                                          \
-        }                                                                        \
-    } while (0)
-
 }  // namespace
 
-int launch_inter_tables_mfma(const epn_inter_desc *d, const float *rk, float *rk4, float *beta, hipStream_t st) {
-    (void)beta; (void)rk;
+int launch_inter_tables_mfma(const epn_inter_desc *d, float *rk4, hipStream_t st) {
     const int n = d->na * EPN_KS_MAX;
     EPN_LAUNCH_AUX(rk4_table_kernel, dim3(epn_cdiv(n, 256)), dim3(256), 0, st, d->anchors, d->kernels, d->na, d->ks,
                    1.0f / d->sigma, rk4);
@@ -1738,13 +1780,11 @@ static bool use8(const epn_inter_desc *d) {
     return d->na >= 16 && d->ks > 16 && d->ks <= 32 && d->nn <= 32;
 }
 
-int launch_inter_fwd_mfma(const epn_inter_desc *d, const float *rk4, const float *beta, const float *feats,
-                          const float *W, float *out, hipStream_t st) {
-    (void)beta;
+int launch_inter_fwd_mfma(const epn_inter_desc *d, const float *rk4, const float *feats, const float *W, float *out,
+                          hipStream_t st) {
     InterArgs A = make_args(d, rk4);
     A.feats = feats; A.W = W; A.out = out;
-    const int mt_ = d->cout / 16;
-    if (use8(d) && (mt_ == 1 || mt_ == 2 || mt_ == 4 || mt_ == 8 || mt_ == 16)) {
+    if (use8(d) && mt_slot(d->cout / 16) >= 0) {
         const int kw1 = d->ks - 16;
         const size_t gsb = (size_t)NW8 * 16 * GS0 * sizeof(float);
         int wk = 16;
@@ -1755,23 +1795,7 @@ int launch_inter_fwd_mfma(const epn_inter_desc *d, const float *rk4, const float
         A.wk = wk;
         const size_t lds = gsb + (size_t)d->cout * (wk + 4) * sizeof(float);
         const unsigned grid = (unsigned)((A.ncol + 16 * NW8 - 1) / (16 * NW8));
-#define EPN_FWD8(NT_, MT_)                                                                              \
-    do {                                                                                                \
-        int rc_ = set_lds(inter_fwd8_kernel<NT_, MT_>, lds);                                            \
-        if (rc_) return rc_;                                                                            \
-        EPN_LAUNCH((inter_fwd8_kernel<NT_, MT_>), dim3(grid), dim3(64 * NW8), lds, st, A);      \
-    } while (0)
-        const int mt = d->cout / 16;
-        if (d->nn <= 16) {
-            if (mt == 4) EPN_FWD8(1, 4); else if (mt == 8) EPN_FWD8(1, 8); else if (mt == 16) EPN_FWD8(1, 16);
-            else if (mt == 2) EPN_FWD8(1, 2); else EPN_FWD8(1, 1);
-        } else {
-            if (mt == 4) EPN_FWD8(2, 4); else if (mt == 8) EPN_FWD8(2, 8); else if (mt == 16) EPN_FWD8(2, 16);
-            else if (mt == 2) EPN_FWD8(2, 2); else EPN_FWD8(2, 1);
-        }
-#undef EPN_FWD8
-        EPN_CHECK_LAUNCH();
-        return 0;
+        return launch_inter(fwd8_kernels[d->nn > 16][mt_slot(d->cout / 16)], dim3(grid), 64 * NW8, lds, st, A);
     }
     const int ckl = 16 * d->ks;
     // W sub-chunk width: largest divisor of the chunk length (multiple of 16) that keeps Ws <= ~56 KB -- and inside what the
@@ -1786,81 +1810,39 @@ int launch_inter_fwd_mfma(const epn_inter_desc *d, const float *rk4, const float
     A.wk = wk;
     const size_t lds = gs_bytes(d) + (size_t)d->cout * (wk + 4) * sizeof(float);
     const unsigned grid = (unsigned)((A.ncol + 16 * NW - 1) / (16 * NW));
-#define EPN_FWD(NT_, KT_, dummy)                                                                      \
-    do {                                                                                              \
-        int rc_ = set_lds(inter_fwd_kernel<NT_, KT_>, lds);                                           \
-        if (rc_) return rc_;                                                                          \
-        EPN_LAUNCH((inter_fwd_kernel<NT_, KT_>), dim3(grid), dim3(64 * NW), lds, st, A);      \
-    } while (0)
-    EPN_DISPATCH_NT_KT(EPN_FWD, 0);
-#undef EPN_FWD
-    EPN_CHECK_LAUNCH();
-    return 0;
+    return launch_inter(fwd_kernels[nt_slot(d)][kt_slot(d)], dim3(grid), 64 * NW, lds, st, A);
 }
 
-int launch_inter_bwd_data_mfma(const epn_inter_desc *d, const float *rk4, const float *WT, const float *dOut,
+// wt_scratch: [cin*ks][cout] floats of workspace for W^T
+int launch_inter_bwd_data_mfma(const epn_inter_desc *d, const float *rk4, float *wt_scratch, const float *dOut,
                                const float *W, float *dF, hipStream_t st) {
-    // WT: scratch [cin*ks][cout] (the caller passes the workspace slot in the `beta` position)
-    float *wt = const_cast<float *>(WT);
     const size_t nW = (size_t)d->cout * d->cin * d->ks;
     EPN_LAUNCH_AUX(transpose_kernel, dim3((unsigned)((nW + 255) / 256)), dim3(256), 0, st, W, d->cout,
-                       d->cin * d->ks, wt);
+                       d->cin * d->ks, wt_scratch);
     EPN_CHECK_LAUNCH();
     InterArgs A = make_args(d, rk4);
-    A.W = wt; A.gout = dOut; A.out = dF;
-    {
-        if (d->na >= 16 && d->nn <= 32 && (d->ks == 24 || d->ks == 32 || d->ks == 16)) {
-            const int pad8 = d->ks == 32 ? 0 : 4;   // MH = 16: unpadded tiles
-            const size_t lds8 = (size_t)4 * 16 * (16 * d->ks + pad8) * sizeof(float) + (size_t)16 * d->ks * (16 + pad8) * sizeof(float);
-            const unsigned grid8 = (unsigned)((A.ncol + 63) / 64);
-#define EPN_BD8(NT_, KT_, MH_)                                                                                 \
-    do {                                                                                                       \
-        int rc_ = set_lds(inter_bwd_data8_kernel<NT_, KT_, MH_>, lds8);                                        \
-        if (rc_) return rc_;                                                                                   \
-        EPN_LAUNCH((inter_bwd_data8_kernel<NT_, KT_, MH_>), dim3(grid8), dim3(64 * NW8), lds8, st, A); \
-    } while (0)
-            if (d->nn <= 16) {
-                if (d->ks == 16) EPN_BD8(1, 1, 8); else if (d->ks == 24) EPN_BD8(1, 2, 12); else EPN_BD8(1, 2, 16);
-            } else {
-                if (d->ks == 16) EPN_BD8(2, 1, 8); else if (d->ks == 24) EPN_BD8(2, 2, 12); else EPN_BD8(2, 2, 16);
-            }
-#undef EPN_BD8
-            EPN_CHECK_LAUNCH();
-            return 0;
-        }
+    A.W = wt_scratch; A.gout = dOut; A.out = dF;
+    if (d->na >= 16 && d->nn <= 32 && (d->ks == 24 || d->ks == 32 || d->ks == 16)) {
+        const int pad8 = d->ks == 32 ? 0 : 4;   // MH = 16: unpadded tiles
+        const size_t lds8 = (size_t)4 * 16 * (16 * d->ks + pad8) * sizeof(float) + (size_t)16 * d->ks * (16 + pad8) * sizeof(float);
+        const unsigned grid8 = (unsigned)((A.ncol + 63) / 64);
+        return launch_inter(bwd_data8_kernels[d->nn > 16][d->ks / 8 - 2], dim3(grid8), 64 * NW8, lds8, st, A);
     }
     const bool tight = d->ks == 32;
     const size_t lds = tight ? (size_t)NW * 16 * 16 * d->ks * sizeof(float) + (size_t)16 * d->ks * 16 * sizeof(float)
                              : gs_bytes(d) + (size_t)16 * d->ks * 20 * sizeof(float);
     const unsigned grid = (unsigned)((A.ncol + 16 * NW - 1) / (16 * NW));
-#define EPN_BD(NT_, KT_, TIGHT_)                                                                              \
-    do {                                                                                                      \
-        int rc_ = set_lds(inter_bwd_data_kernel<NT_, KT_, TIGHT_>, lds);                                      \
-        if (rc_) return rc_;                                                                                  \
-        EPN_LAUNCH((inter_bwd_data_kernel<NT_, KT_, TIGHT_>), dim3(grid), dim3(64 * NW), lds, st, A); \
-    } while (0)
-    if (tight) {
-        const int nt_ = (d->nn + 15) / 16;
-        if (nt_ <= 1) EPN_BD(1, 2, true);
-        else if (nt_ <= 2) EPN_BD(2, 2, true);
-        else if (nt_ <= 4) EPN_BD(4, 2, true);
-        else EPN_BD(8, 2, true);
-    } else {
-        EPN_DISPATCH_NT_KT(EPN_BD, false);
-    }
-#undef EPN_BD
-    EPN_CHECK_LAUNCH();
-    return 0;
+    return launch_inter(tight ? bwd_data_tight_kernels[nt_slot(d)] : bwd_data_kernels[nt_slot(d)][kt_slot(d)], dim3(grid),
+                        64 * NW, lds, st, A);
 }
 
-int launch_inter_bwd_weight_mfma(const epn_inter_desc *d, const float *rk4, const float *beta, const float *feats,
-                                 const float *dOut, float *dW, hipStream_t st) {
-    (void)beta;
+int launch_inter_bwd_weight_mfma(const epn_inter_desc *d, const float *rk4, const float *feats, const float *dOut,
+                                 float *dW, hipStream_t st) {
     InterArgs A = make_args(d, rk4);
     A.feats = feats; A.gout = dOut; A.out = dW;
     // 8-wave kernel: every block of output channels must hold the same power-of-two number of row tiles
     const int mo8 = d->cout >= 128 ? 8 : d->cout / 16;
-    if (use8(d) && d->ks == 24 && (d->cout % 128 == 0 || d->cout == 64 || d->cout == 32)) {
+    if (use8(d) && d->ks == 24 && (d->cout % 128 == 0 || d->cout == 64 || d->cout == 32)) {      // mo8 = 8, 4 or 2
         const long long tiles8 = (A.ncol + 16 * NW8 - 1) / (16 * NW8);
         const int chunks8 = d->cin / 16, oblocks8 = (d->cout + 127) / 128;
         long long splits8 = (256 * 2 + chunks8 * oblocks8 - 1) / (chunks8 * oblocks8);
@@ -1869,21 +1851,8 @@ int launch_inter_bwd_weight_mfma(const epn_inter_desc *d, const float *rk4, cons
         A.col_tiles_per_wg = (int)((tiles8 + splits8 - 1) / splits8);
         const unsigned gx8 = (unsigned)((tiles8 + A.col_tiles_per_wg - 1) / A.col_tiles_per_wg);
         const size_t lds8 = (size_t)NW8 * 16 * GS0 * sizeof(float);
-#define EPN_BW8(NT_, MO_)                                                                                        \
-    do {                                                                                                         \
-        int rc_ = set_lds(inter_bwd_weight8_kernel<NT_, MO_>, lds8);                                             \
-        if (rc_) return rc_;                                                                                     \
-        EPN_LAUNCH((inter_bwd_weight8_kernel<NT_, MO_>), dim3(gx8, chunks8, oblocks8), dim3(64 * NW8),   \
-                           lds8, st, A);                                                                         \
-    } while (0)
-        if (d->nn <= 16) {
-            if (mo8 == 8) EPN_BW8(1, 8); else if (mo8 == 4) EPN_BW8(1, 4); else EPN_BW8(1, 2);
-        } else {
-            if (mo8 == 8) EPN_BW8(2, 8); else if (mo8 == 4) EPN_BW8(2, 4); else EPN_BW8(2, 2);
-        }
-#undef EPN_BW8
-        EPN_CHECK_LAUNCH();
-        return 0;
+        return launch_inter(bwd_weight8_kernels[d->nn > 16][mo8 == 8 ? 2 : (mo8 == 4 ? 1 : 0)], dim3(gx8, chunks8, oblocks8),
+                            64 * NW8, lds8, st, A);
     }
     const long long tiles = (A.ncol + 16 * NW - 1) / (16 * NW);
     const int chunks = d->cin / 16, oblocks = (d->cout + 127) / 128;
@@ -1893,18 +1862,7 @@ int launch_inter_bwd_weight_mfma(const epn_inter_desc *d, const float *rk4, cons
     if (splits < 1) splits = 1;
     A.col_tiles_per_wg = (int)((tiles + splits - 1) / splits);
     const unsigned gx = (unsigned)((tiles + A.col_tiles_per_wg - 1) / A.col_tiles_per_wg);
-    const size_t lds = gs_bytes(d);
-#define EPN_BW(NT_, KT_, dummy)                                                                          \
-    do {                                                                                                 \
-        int rc_ = set_lds(inter_bwd_weight_kernel<NT_, KT_>, lds);                                       \
-        if (rc_) return rc_;                                                                             \
-        EPN_LAUNCH((inter_bwd_weight_kernel<NT_, KT_>), dim3(gx, chunks, oblocks), dim3(64 * NW), \
-                           lds, st, A);                                                                  \
-    } while (0)
-    EPN_DISPATCH_NT_KT(EPN_BW, 0);
-#undef EPN_BW
-    EPN_CHECK_LAUNCH();
-    return 0;
+    return launch_inter(bwd_weight_kernels[nt_slot(d)][kt_slot(d)], dim3(gx, chunks, oblocks), 64 * NW, gs_bytes(d), st, A);
 }
 
 // 16-channel chunks per workgroup of the grouping kernels: the per-point set-up (index row, offsets, weights operand) is
@@ -1930,29 +1888,11 @@ int launch_inter_group_mfma(const epn_inter_desc *d, const float *rk4, const voi
     if (d->na >= 16 && d->cin % 32 == 0 && d->nn <= 64 && (bf16 || d->nn > 16 || packed)) {
         const int cg = d->cin % 64 == 0 ? 4 : 2;
         const unsigned gyw = (unsigned)(d->cin / (16 * cg));
-#define EPN_GRPW(NT_, KT_, dummy)                                                                                              \
-    do {                                                                                                                       \
-        if (bf16 && cg == 4) EPN_LAUNCH((inter_group_wide_kernel<NT_, KT_, __bf16, 4>), dim3(grid, gyw), dim3(64 * NW), 0, st, A); \
-        else if (bf16) EPN_LAUNCH((inter_group_wide_kernel<NT_, KT_, __bf16, 2>), dim3(grid, gyw), dim3(64 * NW), 0, st, A);    \
-        else if (cg == 4) EPN_LAUNCH((inter_group_wide_kernel<NT_, KT_, float, 4>), dim3(grid, gyw), dim3(64 * NW), 0, st, A);  \
-        else EPN_LAUNCH((inter_group_wide_kernel<NT_, KT_, float, 2>), dim3(grid, gyw), dim3(64 * NW), 0, st, A);               \
-    } while (0)
-        EPN_DISPATCH_NT_KT(EPN_GRPW, 0);
-#undef EPN_GRPW
-        EPN_CHECK_LAUNCH();
-        return 0;
+        return launch_inter(group_wide_kernels[bf16 ? 1 : 0][cg == 4][nt_slot(d)][kt_slot(d)], dim3(grid, gyw), 64 * NW, 0, st, A);
     }
     A.col_tiles_per_wg = chunks_per_row(bf16);
     const unsigned gy = (unsigned)(((d->cin >> 4) + A.col_tiles_per_wg - 1) / A.col_tiles_per_wg);
-#define EPN_GRP(NT_, KT_, dummy)                                                                                      \
-    do {                                                                                                              \
-        if (bf16) EPN_LAUNCH((inter_group_kernel<NT_, KT_, __bf16>), dim3(grid, gy), dim3(64 * NW), 0, st, A); \
-        else EPN_LAUNCH((inter_group_kernel<NT_, KT_, float>), dim3(grid, gy), dim3(64 * NW), 0, st, A);      \
-    } while (0)
-    EPN_DISPATCH_NT_KT(EPN_GRP, 0);
-#undef EPN_GRP
-    EPN_CHECK_LAUNCH();
-    return 0;
+    return launch_inter(group_kernels[bf16 ? 1 : 0][nt_slot(d)][kt_slot(d)], dim3(grid, gy), 64 * NW, 0, st, A);
 }
 
 // Column permutation of the weights for packed grouped features.  One thread per element of the PLAIN matrix (coalesced on
@@ -2003,6 +1943,20 @@ static int ungroup_group_points(const epn_inter_desc *d, int nt) {
     return nt <= 1 ? 8 : (nt <= 2 ? (d->p2 % 16 == 0 ? 16 : 8) : (nt <= 4 ? (d->p2 % 8 == 0 ? 8 : 4) : 2));
 }
 
+// the LDS-reduced scatter over groups of gp Morton-adjacent output points (both launchers below): the Morton order, then the
+// instance of scatter_kernels.  canon: the deterministic form's row marks
+static int launch_inter_scatter_mfma(const epn_inter_desc *d, const InterArgs &A, int bf16, int form, int gp, int32_t *order,
+                                     unsigned char *canon, hipStream_t st) {
+    const InterScatterKernel kern = scatter_kernel(d, bf16, form, gp);
+    if (!kern) return EPN_EINVAL;
+    EPN_LAUNCH_AUX(morton_order_kernel, dim3(d->b), dim3(1024), 0, st, d->new_xyz, d->p2, order);
+    EPN_CHECK_LAUNCH();
+    const dim3 grid((unsigned)(d->b * (d->p2 / gp)), (unsigned)((d->cin >> 4) / A.col_tiles_per_wg));
+    EPN_LAUNCH((*kern), grid, dim3(64 * gp), 0, st, A, order, canon);
+    EPN_CHECK_LAUNCH();
+    return 0;
+}
+
 int launch_inter_ungroup_det_mfma(const epn_inter_desc *d, const float *rk4, const void *dG, void *dF, void *slab,
                                   const int32_t *off, const int32_t *ent, int bf16, hipStream_t st, int32_t *order,
                                   unsigned char *canon) {
@@ -2011,65 +1965,30 @@ int launch_inter_ungroup_det_mfma(const epn_inter_desc *d, const float *rk4, con
     const int rowlen = d->na * d->cin, entries = d->p2 * d->nn;
     const long long nred = (long long)d->b * d->p1 * (rowlen >> 2);
     const dim3 g2((unsigned)((nred + 255) / 256));
-    {
-        // pre-reduced form: the LDS-reduced scatter (inter_ungroup_shared_kernel, DET) stores one row per (workgroup,
-        // distinct destination) -- about a third of the per-slot slab -- and the ordered reduction skips the rest
-        const int nt = (d->nn + 15) / 16;
-        const int gp = ungroup_group_points(d, nt);
-        if (order && canon && d->p2 % gp == 0 && d->p2 <= MORTON_MAX && d->p1 <= USH_TAB) {
-            EPN_LAUNCH_AUX(morton_order_kernel, dim3(d->b), dim3(1024), 0, st, d->new_xyz, d->p2, order);
-            EPN_CHECK_LAUNCH();
-            A.col_tiles_per_wg = 1;
-            const dim3 grid((unsigned)(d->b * (d->p2 / gp)), (unsigned)(d->cin >> 4));
-#define EPN_USHD(NT_, KT_, GP_)                                                                                           \
-    do {                                                                                                                  \
-        if (bf16) EPN_LAUNCH((inter_ungroup_shared_kernel<NT_, KT_, __bf16, GP_, ((NT_ == 1 && GP_ == 8) ? 2 : 1), true>), grid, dim3(64 * GP_), 0, st, A, order, canon); \
-        else EPN_LAUNCH((inter_ungroup_shared_kernel<NT_, KT_, float, GP_, ((NT_ == 1 && GP_ == 8) ? 2 : 1), true>), grid, dim3(64 * GP_), 0, st, A, order, canon);      \
-    } while (0)
-            const int kt = (d->ks + 15) / 16;
-            if (kt == 1) {
-                if (nt <= 1) EPN_USHD(1, 1, 8);
-                else if (nt <= 2) { if (gp == 16) EPN_USHD(2, 1, 16); else EPN_USHD(2, 1, 8); }
-                else if (nt <= 4) { if (gp == 8) EPN_USHD(4, 1, 8); else EPN_USHD(4, 1, 4); }
-                else EPN_USHD(8, 1, 2);
-            } else {
-                if (nt <= 1) EPN_USHD(1, 2, 8);
-                else if (nt <= 2) { if (gp == 16) EPN_USHD(2, 2, 16); else EPN_USHD(2, 2, 8); }
-                else if (nt <= 4) { if (gp == 8) EPN_USHD(4, 2, 8); else EPN_USHD(4, 2, 4); }
-                else EPN_USHD(8, 2, 2);
-            }
-#undef EPN_USHD
-            EPN_CHECK_LAUNCH();
-            if (bf16)
-                EPN_LAUNCH_AUX((inter_reduce_slots_kernel<__bf16, __bf16>), g2, dim3(256), 0, st, static_cast<const __bf16 *>(slab),
-                                   off, ent, static_cast<__bf16 *>(dF), d->b, d->p1, entries, rowlen, canon);
-            else
-                EPN_LAUNCH_AUX((inter_reduce_slots_kernel<float, float>), g2, dim3(256), 0, st, static_cast<const float *>(slab),
-                                   off, ent, static_cast<float *>(dF), d->b, d->p1, entries, rowlen, canon);
-            EPN_CHECK_LAUNCH();
-            return 0;
-        }
+    // pre-reduced form: the LDS-reduced scatter (inter_ungroup_shared_kernel, DET) stores one row per (workgroup,
+    // distinct destination) -- about a third of the per-slot slab -- and the ordered reduction skips the rest
+    const int gp = ungroup_group_points(d, (d->nn + 15) / 16);
+    const bool reduced = order && canon && d->p2 % gp == 0 && d->p2 <= MORTON_MAX && d->p1 <= USH_TAB;
+    int rc;
+    if (reduced) {
+        // (form 0 holds every pair ungroup_group_points names)
+        A.col_tiles_per_wg = 1;
+        rc = launch_inter_scatter_mfma(d, A, bf16, 0, gp, order, canon, st);
+    } else {
+        const unsigned grid = (unsigned)((A.ncol + 16 * NW - 1) / (16 * NW));
+        // every wave walks ALL 16-channel chunks of its 16 columns: the [16 anchors][cin] block of a slot is then written by
+        // one wave within a few hundred cycles and leaves L2 as whole lines (chunk-major launch order, which the gather
+        // kernels use for their reads, writes each 128-byte line in 32/64-byte pieces seconds apart: 2x slower, measured)
+        A.col_tiles_per_wg = d->cin >> 4;
+        rc = launch_inter(ungroup_slots_kernels[bf16 ? 1 : 0][nt_slot(d)][kt_slot(d)], dim3(grid, 1), 64 * NW, 0, st, A);
     }
-    const unsigned grid = (unsigned)((A.ncol + 16 * NW - 1) / (16 * NW));
-    // every wave walks ALL 16-channel chunks of its 16 columns: the [16 anchors][cin] block of a slot is then written by
-    // one wave within a few hundred cycles and leaves L2 as whole lines (chunk-major launch order, which the gather
-    // kernels use for their reads, writes each 128-byte line in 32/64-byte pieces seconds apart: 2x slower, measured)
-    A.col_tiles_per_wg = d->cin >> 4;
-    const unsigned gy = 1;
-#define EPN_USLOT(NT_, KT_, dummy)                                                                                       \
-    do {                                                                                                                 \
-        if (bf16) EPN_LAUNCH((inter_ungroup_slots_kernel<NT_, KT_, __bf16>), dim3(grid, gy), dim3(64 * NW), 0, st, A); \
-        else EPN_LAUNCH((inter_ungroup_slots_kernel<NT_, KT_, float>), dim3(grid, gy), dim3(64 * NW), 0, st, A);      \
-    } while (0)
-    EPN_DISPATCH_NT_KT(EPN_USLOT, 0);
-#undef EPN_USLOT
-    EPN_CHECK_LAUNCH();
+    if (rc) return rc;
     if (bf16)
         EPN_LAUNCH_AUX((inter_reduce_slots_kernel<__bf16, __bf16>), g2, dim3(256), 0, st, static_cast<const __bf16 *>(slab),
-                           off, ent, static_cast<__bf16 *>(dF), d->b, d->p1, entries, rowlen);
+                           off, ent, static_cast<__bf16 *>(dF), d->b, d->p1, entries, rowlen, reduced ? canon : nullptr);
     else
         EPN_LAUNCH_AUX((inter_reduce_slots_kernel<float, float>), g2, dim3(256), 0, st, static_cast<const float *>(slab),
-                           off, ent, static_cast<float *>(dF), d->b, d->p1, entries, rowlen);
+                           off, ent, static_cast<float *>(dF), d->b, d->p1, entries, rowlen, reduced ? canon : nullptr);
     EPN_CHECK_LAUNCH();
     return 0;
 }
@@ -2101,8 +2020,6 @@ int launch_inter_ungroup_mfma(const epn_inter_desc *d, const float *rk4, const v
     // the 16-point form there (1.64 -> 1.43 ms); with 64-channel groups 16 points stay ahead (1.26 vs 1.75 fp32, 1.39 vs 1.45 bf16)
     if (nt == 2 && d->cin % 64 != 0 && d->cin % 32 == 0 && d->p2 % 8 == 0) gp = 8;
     if (order && d->p2 % gp == 0 && d->p2 <= MORTON_MAX && d->p1 <= USH_TAB && kernel_policy() != (0x400 | 1)) {
-        EPN_LAUNCH_AUX(morton_order_kernel, dim3(d->b), dim3(1024), 0, st, d->new_xyz, d->p2, order);
-        EPN_CHECK_LAUNCH();
         // Chunks per anchor step: the weights of an anchor are generated once for CW * CS chunks; CW of them share one
         // barrier pair (LDS tile 16 CW channels wide), CS such groups follow each other on the same tile.
         // Measured per layer (ms, one chunk per step -> grouped): CW = 4: fp32 K = 16 1.93 -> 1.77, K = 32 1.36 -> 1.26;
@@ -2113,53 +2030,14 @@ int launch_inter_ungroup_mfma(const epn_inter_desc *d, const float *rk4, const v
         // (and the 32-channel K = 32 layers, which the four-chunk form does not take)
         const bool wide2 = !wide && d->cin % 32 == 0 && ((nt > 2 && nt <= 4 && gp == 8) || nt == 2);
         A.col_tiles_per_wg = wide ? 4 : (wide2 ? 2 : 1);   // (CS = 4 at K = 64 measured 1.50 -> 1.73 ms: not instantiated)
-        const dim3 grid((unsigned)(d->b * (d->p2 / gp)), (unsigned)((d->cin >> 4) / A.col_tiles_per_wg));
-#define EPN_USH(NT_, KT_, GP_)                                                                                            \
-    do {                                                                                                                  \
-        constexpr int nb_ = ((NT_ == 1 && GP_ == 8) ? 2 : 1);                                                             \
-        if (wide) {                                                                                                       \
-            if constexpr (NT_ <= 2) {                                                                                     \
-                if (bf16) EPN_LAUNCH((inter_ungroup_shared_kernel<NT_, KT_, __bf16, GP_, nb_, false, 4, 1>), grid, dim3(64 * GP_), 0, st, A, order); \
-                else EPN_LAUNCH((inter_ungroup_shared_kernel<NT_, KT_, float, GP_, nb_, false, 4, 1>), grid, dim3(64 * GP_), 0, st, A, order);      \
-            }                                                                                                             \
-        } else if (wide2) {                                                                                               \
-            if constexpr ((NT_ == 4 && GP_ == 8) || NT_ == 2) {                                                           \
-                if (bf16) EPN_LAUNCH((inter_ungroup_shared_kernel<NT_, KT_, __bf16, GP_, nb_, false, 2, 1>), grid, dim3(64 * GP_), 0, st, A, order); \
-                else EPN_LAUNCH((inter_ungroup_shared_kernel<NT_, KT_, float, GP_, nb_, false, 2, 1>), grid, dim3(64 * GP_), 0, st, A, order);      \
-            }                                                                                                             \
-        } else {                                                                                                          \
-            if (bf16) EPN_LAUNCH((inter_ungroup_shared_kernel<NT_, KT_, __bf16, GP_, nb_>), grid, dim3(64 * GP_), 0, st, A, order); \
-            else EPN_LAUNCH((inter_ungroup_shared_kernel<NT_, KT_, float, GP_, nb_>), grid, dim3(64 * GP_), 0, st, A, order);      \
-        }                                                                                                                 \
-    } while (0)
-        const int kt = (d->ks + 15) / 16;
-        if (kt == 1) {
-            if (nt <= 1) EPN_USH(1, 1, 8);
-            else if (nt <= 2) { if (gp == 16) EPN_USH(2, 1, 16); else EPN_USH(2, 1, 8); }
-            else if (nt <= 4) { if (gp == 8) EPN_USH(4, 1, 8); else EPN_USH(4, 1, 4); }
-            else EPN_USH(8, 1, 2);
-        } else {
-            if (nt <= 1) EPN_USH(1, 2, 8);
-            else if (nt <= 2) { if (gp == 16) EPN_USH(2, 2, 16); else EPN_USH(2, 2, 8); }
-            else if (nt <= 4) { if (gp == 8) EPN_USH(4, 2, 8); else EPN_USH(4, 2, 4); }
-            else EPN_USH(8, 2, 2);
-        }
-#undef EPN_USH
-        EPN_CHECK_LAUNCH();
-        return 0;
+        // The table has what these conditions ask for: `wide` says nt <= 2, and form 3 (CW = 4) holds every pair of NT = 1, 2;
+        // `wide2` says nt == 2 -- pairs (2, 16) and (2, 8) -- or NT = 4 with gp == 8 -- pair (4, 8): the three of form 2.
+        return launch_inter_scatter_mfma(d, A, bf16, wide ? 3 : (wide2 ? 2 : 1), gp, order, nullptr, st);
     }
     const unsigned grid = (unsigned)((A.ncol + 16 * NW - 1) / (16 * NW));
     A.col_tiles_per_wg = 1;
     const unsigned gy = (unsigned)(((d->cin >> 4) + A.col_tiles_per_wg - 1) / A.col_tiles_per_wg);
-#define EPN_UGRP(NT_, KT_, dummy)                                                                                       \
-    do {                                                                                                                \
-        if (bf16) EPN_LAUNCH((inter_ungroup_kernel<NT_, KT_, __bf16>), dim3(grid, gy), dim3(64 * NW), 0, st, A); \
-        else EPN_LAUNCH((inter_ungroup_kernel<NT_, KT_, float>), dim3(grid, gy), dim3(64 * NW), 0, st, A);      \
-    } while (0)
-    EPN_DISPATCH_NT_KT(EPN_UGRP, 0);
-#undef EPN_UGRP
-    EPN_CHECK_LAUNCH();
-    return 0;
+    return launch_inter(ungroup_kernels[bf16 ? 1 : 0][nt_slot(d)][kt_slot(d)], dim3(grid, gy), 64 * NW, 0, st, A);
 }
 
 }  // namespace epn

@@ -1,4 +1,5 @@
-"""Case tables of the exact convolution tests (tests/test_gpu_conv_exact.py, tests/test_conv_spec.py) and a restatement of the
+"""Case tables of the exact convolution tests (tests/test_gpu_conv_exact.py, tests/test_conv_spec.py), of the instance tests of the
+grouping entries (tests/test_gpu_group_dispatch.py) and a restatement of the
 dispatch of csrc/inter_mfma.hip and csrc/intra_mfma.hip: which kernel instance epn_last_kernel() must name for a descriptor and a
 pass.  Nothing here needs a device; only the real-geometry builders need the package and the CPU oracle.
 
@@ -9,6 +10,7 @@ alpha_n + beta_k + g . r is then a multiple of 1/16 of a few bits, w is the same
 partial sum of out, dF and dW stays below 2^24 last-bit units -- build_inter() PROVES the last two statements for the case it
 returns (assertions on float64 sums), tests/test_conv_spec.py the first."""
 import itertools
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -21,14 +23,41 @@ EPN_KS_MAX, EPN_NN_MAX = 32, 128
 
 _CACHE = {}
 InterCase = namedtuple("InterCase", "name nn ks cin cout na b p2 passes sigma p1", defaults=(PASSES, 0.25, 6))
+GroupCase = namedtuple("GroupCase", "name nn ks cin na p2 b p1 sigma", defaults=(2, 6, 0.25))
+InvCase = namedtuple("InvCase", "name b p1 p2 nn")
 IntraCase = namedtuple("IntraCase", "name kn cin cout na b p", defaults=(2, 3))
 
 
 def normalise(name):
-    """epn_last_kernel()'s text -> the spelling used here: no namespace, no blanks."""
+    """epn_last_kernel()'s text -> the spelling used here: no namespace, no blanks.  A name the C++ runtime could not demangle
+    (it does not know DF16b, the bf16 type of the grouping kernels' template arguments) comes back mangled and is read here."""
     if isinstance(name, bytes):
         name = name.decode()
-    return name.replace("epn::", "").replace(" ", "")
+    if name.startswith("_Z"):
+        name = _demangle(name)
+    # ... and ONE such name it does demangle, wrongly: `DF16b Li2E Li1E` (bf16, GP = 2, NB = 1: the K = 128 scatter) is read as a
+    # fixed-point type and the two integers are lost.  No other instance has that text (tests/test_conv_spec.py).
+    return name.replace("epn::", "").replace(" ", "").replace("bool_Accum,int,EL,int,E", "__bf16,2,1")
+
+
+def _demangle(m):
+    """_ZN3epn12_GLOBAL__N_1<len><kernel>I<args>E...: a kernel template of the library's anonymous namespace whose arguments are
+    integers, booleans, float or bf16."""
+    mo = re.match(r"_ZN3epn12_GLOBAL__N_1(\d+)", m)
+    if not mo:
+        raise ValueError(m)
+    start = mo.end()
+    kernel, rest = m[start:start + int(mo.group(1))], m[start + int(mo.group(1)):]
+    if not rest.startswith("I"):
+        return kernel
+    rest, args = rest[1:], []
+    while not rest.startswith("E"):
+        mo = re.match(r"Li(\d+)E|Lb([01])E|(f)|(DF16b)", rest)
+        if not mo:
+            raise ValueError(m)
+        args.append(mo.group(1) or (("false", "true")[int(mo.group(2))] if mo.group(2) else "float" if mo.group(3) else "__bf16"))
+        rest = rest[mo.end():]
+    return f"{kernel}<{','.join(args)}>"
 
 
 # ------------------------------------------------------------------------------------------------ dispatch restatement
@@ -49,7 +78,7 @@ def use8(c):
 
 
 def _nt(nn):
-    """EPN_DISPATCH_NT_KT: neighbour tiles of 16, rounded up to 1, 2, 4, 8."""
+    """inter_mfma.hip nt_slot: neighbour tiles of 16, rounded up to 1, 2, 4, 8."""
     t = (nn + 15) // 16
     return 1 if t <= 1 else 2 if t <= 2 else 4 if t <= 4 else 8
 
@@ -115,6 +144,104 @@ def intra_weight_grad_plan(c):
     return tiles, (tiles + splits - 1) // splits
 
 
+# ---- grouping and its transposes (launch_inter_group_mfma, launch_inter_ungroup_mfma, launch_inter_ungroup_det_mfma and
+# launch_inverse_list of inter_mfma.hip behind the epn_inter_group* / epn_inter_ungroup* / epn_inter_inverse_list entries)
+MORTON_MAX = USH_TAB = 4096
+INV_LDS_ENT, INV_LDS_P1 = 32768, 4096
+EPN_EINVAL = -1
+
+
+def group_is_mfma(c):
+    """conv_internal.h inter_group_mfma_ok (anything else takes the generic kernels of conv_generic.hip)."""
+    return c.cin % 16 == 0 and c.ks <= EPN_KS_MAX and c.ks % 4 == 0 and c.nn <= EPN_NN_MAX and c.p1 * c.na * c.cin < 2 ** 31
+
+
+def group_packed_ok(c):
+    """conv_internal.h inter_group_packed_ok."""
+    return group_is_mfma(c) and c.na >= 16 and c.cin % 32 == 0 and c.nn <= 64
+
+
+def _tg(bf16):
+    return "__bf16" if bf16 else "float"
+
+
+def group_instance(c, bf16, packed):
+    """Instance of epn_inter_group{,_packed}_{f32,bf16}; None: the entry refuses the shape (EPN_EINVAL)."""
+    assert group_is_mfma(c), c
+    if packed and not group_packed_ok(c):
+        return None
+    nt, kt = _nt(c.nn), 1 if (c.ks + 15) // 16 == 1 else 2
+    if c.na >= 16 and c.cin % 32 == 0 and c.nn <= 64 and (bf16 or c.nn > 16 or packed):
+        return f"inter_group_wide_kernel<{nt},{kt},{_tg(bf16)},{4 if c.cin % 64 == 0 else 2}>"
+    return f"inter_group_kernel<{nt},{kt},{_tg(bf16)}>"
+
+
+def ungroup_group_points(c):
+    """inter_mfma.hip ungroup_group_points: output points per workgroup of the LDS-reduced scatter."""
+    nt = (c.nn + 15) // 16
+    return 8 if nt <= 1 else (16 if c.p2 % 16 == 0 else 8) if nt <= 2 else (8 if c.p2 % 8 == 0 else 4) if nt <= 4 else 2
+
+
+def _shared_ok(c, gp):
+    return c.p2 % gp == 0 and c.p2 <= MORTON_MAX and c.p1 <= USH_TAB
+
+
+def _shared(c, bf16, gp, det, cw):
+    nt, kt = _nt(c.nn), 1 if (c.ks + 15) // 16 == 1 else 2
+    nb = 2 if nt == 1 and gp == 8 else 1
+    return f"inter_ungroup_shared_kernel<{nt},{kt},{_tg(bf16)},{gp},{nb},{'true' if det else 'false'},{cw},1>"
+
+
+def ungroup_plan(c):
+    """(points per workgroup, chunks per anchor step) of the LDS-reduced scatter of launch_inter_ungroup_mfma, or None where
+    the per-slot atomic scatter runs (p2 no multiple of the group, or beyond the Morton sort / the destination table)."""
+    nt = (c.nn + 15) // 16
+    gp = ungroup_group_points(c)
+    if nt == 2 and c.cin % 64 != 0 and c.cin % 32 == 0 and c.p2 % 8 == 0:
+        gp = 8
+    if not _shared_ok(c, gp):
+        return None
+    wide = c.cin % 64 == 0 and nt <= 2
+    wide2 = not wide and c.cin % 32 == 0 and ((2 < nt <= 4 and gp == 8) or nt == 2)
+    return gp, 4 if wide else 2 if wide2 else 1
+
+
+def ungroup_instance(c, bf16):
+    """Instance of epn_inter_ungroup_{f32,bf16} (default kernel policy; the entries always pass the Morton-order scratch)."""
+    assert group_is_mfma(c), c
+    plan = ungroup_plan(c)
+    if plan is None:
+        return f"inter_ungroup_kernel<{_nt(c.nn)},{1 if (c.ks + 15) // 16 == 1 else 2},{_tg(bf16)}>"
+    return _shared(c, bf16, plan[0], False, plan[1])
+
+
+def ungroup_det_instance(c, bf16):
+    """Instance of epn_inter_ungroup_det_{f32,bf16} given a slab with room for the row marks; None: refused (c_api.hip: fewer
+    than 16 anchors, or rows that are no multiple of four floats)."""
+    assert group_is_mfma(c), c
+    if c.na < 16 or (c.na * c.cin) % 4:
+        return None
+    gp = ungroup_group_points(c)
+    if _shared_ok(c, gp):
+        return _shared(c, bf16, gp, True, 1)
+    return f"inter_ungroup_slots_kernel<{_nt(c.nn)},{1 if (c.ks + 15) // 16 == 1 else 2},{_tg(bf16)}>"
+
+
+def inverse_list_instance(c):
+    """launch_inverse_list: the counting sort in LDS while a cloud's entries and points fit it."""
+    return "inverse_list_lds_kernel" if c.p2 * c.nn <= INV_LDS_ENT and c.p1 <= INV_LDS_P1 else "inverse_list_kernel"
+
+
+def packed_position(cin, ks):
+    """conv_internal.h inter_packed_position for every plain column c * ks + k."""
+    cg = 4 if cin % 64 == 0 else 2
+    c, k = np.divmod(np.arange(cin * ks), ks)
+    cl = c % (16 * cg)
+    slot = c - cl + 16 * (cl % cg) + cl // cg
+    w0 = min(ks, 16)
+    return np.where(k < 16, slot * w0 + k, w0 * cin + slot * (ks - 16) + (k - 16))
+
+
 # Every instance the launchers can reach.  (No instance of the two files is unreachable: the 4-wave forward and data-gradient
 # kernels at ks = 32, and the 8-wave data gradient <*, 2, 16>, asked for more than the 160 KB of LDS until this table was
 # written -- CHANGELOG -- and are reachable since.)
@@ -129,6 +256,24 @@ REACHABLE = {
     ("intra", "fwd"): {"intra_gemm_kernel"},
     ("intra", "bwd_data"): {"intra_gemm_kernel"},
     ("intra", "bwd_weight"): {"intra_bwd_weight_kernel", "intra_bwd_weight_v4_kernel", "intra_bwd_weight_pt_kernel"},
+}
+# The grouping families (a dictionary of their own: the keys of REACHABLE are (layer, pass)).  Instantiated in inter_mfma.hip but out of the launchers' reach, hence not listed: the wide grouping with
+# NT = 8 (it is asked for at nn <= 64 only) and the scatter <2, *, *, 16, 1, false, 2, 1> (two chunks per step at NT = 2 means
+# cin % 64 = 32, where a p2 that 16 divides is moved to groups of 8).
+_NK = [(n, k) for n in (1, 2, 4, 8) for k in (1, 2)]
+_T = ("float", "__bf16")
+_GROUPS = ((1, 8, 2), (2, 16, 1), (2, 8, 1), (4, 8, 1), (4, 4, 1), (8, 2, 1))        # (NT, GP, NB) of the LDS-reduced scatter
+REACHABLE_GROUPING = {
+    "group": {f"inter_group_kernel<{n},{k},{t}>" for n, k in _NK for t in _T}
+             | {f"inter_group_wide_kernel<{n},{k},{t},{g}>" for n, k in _NK if n <= 4 for t in _T for g in (2, 4)},
+    "ungroup": {f"inter_ungroup_kernel<{n},{k},{t}>" for n, k in _NK for t in _T}
+               | {f"inter_ungroup_shared_kernel<{n},{k},{t},{gp},{nb},false,{cw},1>" for n, gp, nb in _GROUPS for k in (1, 2)
+                  for t in _T for cw in (1, 2, 4)
+                  if cw == 1 or (cw == 4 and n <= 2) or (cw == 2 and (n, gp) in ((2, 8), (4, 8)))},
+    "ungroup_det": {f"inter_ungroup_slots_kernel<{n},{k},{t}>" for n, k in _NK for t in _T}
+                   | {f"inter_ungroup_shared_kernel<{n},{k},{t},{gp},{nb},true,1,1>" for n, gp, nb in _GROUPS for k in (1, 2)
+                      for t in _T},
+    "inverse_list": {"inverse_list_lds_kernel", "inverse_list_kernel"},
 }
 
 # ------------------------------------------------------------------------------------------------ the cases
@@ -199,6 +344,29 @@ INTRA_CASES = [
     # workgroup one
     J("kn4_256_256_pt_points", 4, 256, 256, 60, 3, 13),
 ]
+
+# Grouping and its transposes: the smallest shapes at which the launchers' choice can go wrong, one per reachable instance and
+# edge.  Two clouds of p1 = 6 points; ks = 12 takes the lower side of every neighbour-count edge (16 | 17, 32 | 33, 64 | 65),
+# ks = 24 the upper one (and 128); cin = 16 / 32 / 64 = narrow grouping and one chunk per scatter step / CG = 2 and two chunks /
+# CG = 4 and four; p2 = 16, 8, 4 are the scatter's group sizes and 3 is a multiple of none (per-slot atomic scatter, slot-slab
+# deterministic form); na = 12 is refused by the wide grouping, the packed order and the deterministic entry.
+def _group_cases():
+    out = []
+    for ks, (n1, n2, n4, n8) in ((12, (16, 17, 33, 65)), (24, (16, 32, 64, 128))):
+        for nn, cin, na, p2 in (
+                (n1, 16, 60, 8), (n1, 32, 60, 3), (n1, 64, 60, 8), (n1, 32, 12, 8),
+                (n2, 64, 60, 16), (n2, 64, 60, 8), (n2, 32, 60, 16), (n2, 16, 60, 16), (n2, 16, 60, 8), (n2, 32, 60, 3),
+                (n2, 64, 12, 16),
+                (n4, 32, 60, 8), (n4, 16, 60, 8), (n4, 64, 60, 4), (n4, 16, 60, 3),
+                (n8, 16, 60, 4), (n8, 16, 60, 3), (n8, 32, 60, 2)):
+            out.append(GroupCase(f"k{ks}_n{nn}_c{cin}_a{na}_p{p2}", nn, ks, cin, na, p2))
+    return out
+
+
+GROUP_CASES = _group_cases()
+# both sides of INV_LDS_ENT (entries of a cloud) and of INV_LDS_P1 (points of a cloud); one cloud is enough for the large ones
+INV_CASES = [InvCase("small", 2, 6, 3, 16), InvCase("ent_32768", 1, 300, 256, 128), InvCase("ent_32896", 1, 300, 257, 128),
+             InvCase("p1_4096", 2, 4096, 5, 16), InvCase("p1_4097", 2, 4097, 5, 16)]
 
 # Real-geometry tier: (name, schedule, layer, cin, cout, points per cloud) -- nn, stride, radius and sigma are the layer's: the
 # first layer of the classification schedule (nn = 32: the 8-wave kernels) and a K = 64 layer of the rotation-estimation one
@@ -325,6 +493,37 @@ def build_inter(c, seed=None):
                 **ops)
 
 
+def _bf16(v):
+    """float32 values rounded to the nearest bf16 (ties to even), so that one operand serves the fp32 and the bf16 entries."""
+    u = np.ascontiguousarray(v, np.float32).view(np.uint32)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32)
+
+
+def build_group(c):
+    """A grouping case: the dyadic geometry of build_inter (the weights are then the same float in every form), features F and a
+    grouped gradient dG of bf16-representable normal deviates, and the float64 G = group(F), dF = ungroup(dG)."""
+    rng = np.random.default_rng(hash_name(c.name))
+    anchors = _rotations24()[np.arange(c.na) % 24].astype(np.float32)
+    eighth = lambda shape, m: (rng.integers(-m, m + 1, size=shape) / 8.0).astype(np.float32)
+    kernels = eighth((c.ks, 3), 2)
+    xyz, new_xyz = eighth((c.b, 3, c.p1), 2), eighth((c.b, 3, c.p2), 2)
+    idx = _index_table(rng, c)
+    F = _bf16(rng.standard_normal((c.b, c.p1, c.na, c.cin)))
+    dG = _bf16(rng.standard_normal((c.b * c.p2 * c.na, c.cin * c.ks)))
+    geo = (xyz, new_xyz, idx, anchors, kernels, c.sigma)
+    return dict(xyz=xyz, new_xyz=new_xyz, idx=idx, anchors=anchors, kernels=kernels, sigma=c.sigma, F=F, dG=dG,
+                G=R.inter_group(*geo, F), dF=R.inter_ungroup(*geo, dG, c.cin))
+
+
+def build_inverse(c):
+    """An index table [b, p2, nn] with indices up to p1 + 2 (p1 and beyond: shadow) and one point named by a whole row."""
+    rng = np.random.default_rng(hash_name(c.name))
+    idx = rng.integers(0, c.p1 + 3, size=(c.b, c.p2, c.nn)).astype(np.int32)
+    idx[0, 0, :] = c.p1 - 1
+    off, ent = R.inverse_list(idx, c.p1)
+    return dict(idx=idx, off=off, ent=ent)
+
+
 def build_intra(c):
     rng = np.random.default_rng(abs(hash_name(c.name)))
     idx = np.stack([rng.permutation(c.na) for _ in range(c.kn)], axis=1).astype(np.int32)
@@ -355,4 +554,10 @@ def inter_case(c):
 def intra_case(c):
     if c not in _CACHE:
         _CACHE[c] = build_intra(c)
+    return _CACHE[c]
+
+
+def group_case(c):
+    if c not in _CACHE:
+        _CACHE[c] = build_group(c) if isinstance(c, GroupCase) else build_inverse(c)
     return _CACHE[c]

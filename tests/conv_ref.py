@@ -64,6 +64,43 @@ def _scatter(w, W3, gOut, safe, fshape):
     return dF
 
 
+def inter_group(xyz, new_xyz, ball_idx, anchors, kernels, sigma, F):
+    """The gather of inter_conv on its own, as the matrix the grouping entries write in the plain column order:
+      G[(b, p, a), c * ks + k] = sum_n F[b, idx[b, p, n], a, c] w[b, p, a, k, n]"""
+    w, g, valid, safe, rk = inter_weights(xyz, new_xyz, ball_idx, anchors, kernels, sigma)
+    F = np.asarray(F, F64)
+    Fg = F[np.arange(F.shape[0])[:, None, None], safe]                                         # [b, p, n, a, c]
+    G = np.einsum("bpnac,bpakn->bpack", Fg, w, optimize=True)
+    return G.reshape(-1, F.shape[3] * w.shape[3])
+
+
+def inter_ungroup(xyz, new_xyz, ball_idx, anchors, kernels, sigma, dG, cin):
+    """The transpose of inter_group: dF[b, q, a, c] = sum_{p, n : idx[b, p, n] = q} sum_k w[b, p, a, k, n] dG[(b, p, a), c * ks + k]"""
+    w, g, valid, safe, rk = inter_weights(xyz, new_xyz, ball_idx, anchors, kernels, sigma)
+    b, p2, na, ks, nn = w.shape
+    T = np.einsum("bpakn,bpack->bpnac", w, np.asarray(dG, F64).reshape(b, p2, na, cin, ks), optimize=True)
+    dF = np.zeros((b, np.asarray(xyz).shape[2], na, cin))
+    for bb in range(b):
+        np.add.at(dF[bb], safe[bb].reshape(-1), T[bb].reshape(-1, na, cin))                    # (shadow slots carry w = 0)
+    return dF
+
+
+def inverse_list(ball_idx, p1):
+    """(off[b, p1 + 1], ent[b, p2 * nn]) of epn_inter_inverse_list: per cloud the CSR inverse of the index table -- the entries
+    p * nn + n that name a point, by point, then ascending; indices outside 0 .. p1 - 1 dropped, the tail of ent -1."""
+    idx = np.asarray(ball_idx)
+    b = idx.shape[0]
+    off = np.zeros((b, p1 + 1), np.int32)
+    ent = np.full((b, idx.shape[1] * idx.shape[2]), -1, np.int32)
+    for bb in range(b):
+        flat = idx[bb].reshape(-1)
+        valid = np.nonzero((flat >= 0) & (flat < p1))[0]
+        order = valid[np.argsort(flat[valid], kind="stable")]
+        off[bb, 1:] = np.cumsum(np.bincount(flat[valid], minlength=p1))
+        ent[bb, :len(order)] = order
+    return off, ent
+
+
 def inter_abs_sums(xyz, new_xyz, ball_idx, anchors, kernels, sigma, F, W, gOut, expanded=False, want=("out", "dF", "dW")):
     """Sums of ABSOLUTE values of the terms of every element of out, dF and dW -- what the largest partial sum of any summation
     order is bounded by.  expanded: w is replaced by w + |g|^2 / sigma + |g . r| + |beta| (r = (2 / sigma) R_a kappa_k,

@@ -1,7 +1,8 @@
 """What tests/test_gpu_conv_exact.py relies on, pinned without a device: the dyadic cases of tests/conv_cases.py are exact in
 fp32 in every evaluation order, have headroom, are not vacuous; the float64 restatement of tests/conv_ref.py agrees with the fp32
 oracle and the golden file; the dispatch restatement agrees with the library's host-side answers and covers every instance and
-every edge value; REAL_M is what the oracle's own error gives."""
+every edge value -- of the fused passes and, for tests/test_gpu_group_dispatch.py, of the grouping entries; REAL_M is what the
+oracle's own error gives."""
 import math
 
 import numpy as np
@@ -208,6 +209,78 @@ def test_cases_reach_every_instance_and_every_edge_value():
     for name in ("kn13_128_128_v4_tiles", "kn13_48_128_tiles", "kn1_256_256_v4_tiles"):
         tiles, per = C.intra_weight_grad_plan(next(c for c in C.INTRA_CASES if c.name == name))
         assert per > 1 and tiles % per != 0, (name, tiles, per)
+
+
+def _group_calls(c):
+    """(family, restated instance or None) of the eight calls tests/test_gpu_group_dispatch.py makes for a grouping case."""
+    for bf16 in (0, 1):
+        for packed in (0, 1):
+            yield "group", C.group_instance(c, bf16, packed)
+        yield "ungroup", C.ungroup_instance(c, bf16)
+        yield "ungroup_det", C.ungroup_det_instance(c, bf16)
+
+
+def test_group_cases_reach_every_instance_and_every_edge_value():
+    sizes = dict(group=16 + 24, ungroup=16 + 44, ungroup_det=16 + 24, inverse_list=2)
+    for key, want in sizes.items():
+        assert len(C.REACHABLE_GROUPING[key]) == want                                  # no instance listed twice, none forgotten
+    seen = {key: set() for key in sizes}
+    for c in C.GROUP_CASES:
+        for key, name in _group_calls(c):
+            assert name is None or name in C.REACHABLE_GROUPING[key], (c, name)
+            seen[key].add(name)
+    seen["inverse_list"] = {C.inverse_list_instance(c) for c in C.INV_CASES}
+    for key in sizes:
+        assert seen[key] - {None} == C.REACHABLE_GROUPING[key], (key, C.REACHABLE_GROUPING[key] ^ (seen[key] - {None}))
+    # the refusals: the packed order where the wide kernel does not serve, the deterministic entry below 16 anchors
+    assert None in seen["group"] and None in seen["ungroup_det"] and None not in seen["ungroup"]
+    assert len({c.name for c in C.GROUP_CASES}) == len(C.GROUP_CASES)
+    assert {c.nn for c in C.GROUP_CASES} >= {16, 17, 32, 33, 64, 65, 128} and {c.ks for c in C.GROUP_CASES} == {12, 24}
+    assert {c.cin for c in C.GROUP_CASES} == {16, 32, 64} and {c.na for c in C.GROUP_CASES} == {60, 12}
+    assert {c.p2 for c in C.GROUP_CASES} >= {16, 8, 4, 3} and all(c.b == 2 for c in C.GROUP_CASES)
+    # both scatters and both fallbacks, two and four chunks per step, every group size
+    plans = {C.ungroup_plan(c) for c in C.GROUP_CASES}
+    assert plans >= {None} | {(gp, 1) for gp in (16, 8, 4, 2)} | {(8, 2), (8, 4), (16, 4)}
+    # the 32-channel K = 32 case whose p2 16 divides is moved to groups of 8: the one pair the two-chunk form is never asked for
+    assert any(C.ungroup_group_points(c) == 16 and C.ungroup_plan(c) == (8, 2) for c in C.GROUP_CASES)
+    assert (16, 2) not in plans
+    ent = {c.p2 * c.nn for c in C.INV_CASES}
+    assert {C.INV_LDS_ENT, C.INV_LDS_ENT + 128} <= ent and {C.INV_LDS_P1, C.INV_LDS_P1 + 1} <= {c.p1 for c in C.INV_CASES}
+
+
+def test_normalise_reads_the_names_the_runtime_leaves_mangled():
+    n = C.normalise
+    assert n(b"epn::inter_group_kernel<1, 2, float>") == "inter_group_kernel<1,2,float>"
+    assert n(b"_ZN3epn12_GLOBAL__N_118inter_group_kernelILi1ELi1EDF16bEEvNS0_9InterArgsE") == "inter_group_kernel<1,1,__bf16>"
+    assert n(b"_ZN3epn12_GLOBAL__N_127inter_ungroup_shared_kernelILi2ELi1EDF16bLi16ELi1ELb0ELi4ELi1EEEvNS0_9InterArgsEPKiPh") \
+        == "inter_ungroup_shared_kernel<2,1,__bf16,16,1,false,4,1>"
+    assert n(b"_ZN3epn12_GLOBAL__N_127inter_ungroup_shared_kernelILi1ELi1EfLi8ELi2ELb1ELi1ELi1EEEvNS0_9InterArgsEPKiPh") \
+        == "inter_ungroup_shared_kernel<1,1,float,8,2,true,1,1>"
+    assert n(b"_ZN3epn12_GLOBAL__N_119inverse_list_kernelEPKiiiPiS3_") == "inverse_list_kernel"
+    assert n(b"epn::inter_ungroup_shared_kernel<8, 1, bool _Accum, int, EL, int, E, false, 1, 1>") \
+        == "inter_ungroup_shared_kernel<8,1,__bf16,2,1,false,1,1>"
+    assert sum("__bf16,2,1," in name for fam in C.REACHABLE_GROUPING.values() for name in fam) == 4       # <8, 1 | 2, .., false | true>
+    with pytest.raises(ValueError):
+        n(b"_ZN3epn12_GLOBAL__N_118inter_group_kernelILi1ELi1EdEEvNS0_9InterArgsE")
+
+
+def test_group_cases_stay_within_what_the_entries_accept():
+    from epn_pointcloud_amd import _lib
+    lib = _lib.get_lib()
+    keep = np.zeros(16, np.float32)
+    for c in C.GROUP_CASES:
+        assert C.group_is_mfma(c) and 1 <= c.p2 <= C.MORTON_MAX and 1 <= c.p1 <= C.USH_TAB, c
+        d = _lib.InterDesc()
+        d.xyz = d.new_xyz = d.ball_idx = d.anchors = d.kernels = keep.ctypes.data
+        d.dense_w, d.sigma = None, c.sigma
+        d.b, d.p1, d.p2, d.nn, d.na, d.ks, d.cin, d.cout = c.b, c.p1, c.p2, c.nn, c.na, c.ks, c.cin, 16
+        assert bool(lib.epn_inter_group_packed_ok(d)) == C.group_packed_ok(c), c
+        if C.group_packed_ok(c):
+            pos = np.empty(c.cin * c.ks, np.int32)
+            assert lib.epn_inter_packed_position(c.cin, c.ks, pos.ctypes.data) == 0
+            assert np.array_equal(pos, C.packed_position(c.cin, c.ks)), c
+    for c in C.INV_CASES:
+        assert c.b >= 1 and c.p1 >= 1 and c.p2 >= 0 and c.nn >= 1 and c.p2 * c.nn < 2 ** 20
 
 
 # ------------------------------------------------------------------------------------------------ REAL_M from the oracle
