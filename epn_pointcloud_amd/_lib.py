@@ -61,6 +61,7 @@ EXPORTS = [
     "epn_voxel_downsample_workspace_bytes", "epn_voxel_downsample_f32",
     "epn_rotation_labels_f32", "epn_so3_mean_f32", "epn_rotation_decode_f32",
     "epn_ransac_register_workspace_bytes", "epn_ransac_register_f64",
+    "epn_triplet_batch_hard_f32", "epn_triplet_batch_hard_bwd_f32", "epn_anchor_interp_f32", "epn_anchor_interp_bwd_f32",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -336,6 +337,14 @@ def get_lib():
                                             ctypes.c_uint64, ctypes.c_int64, ctypes.c_double, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp]
     lib.epn_ransac_register_f64.restype = _ci
+    # training loss of the descriptor network: (src, tgt, N, D, mode, margin, eps, six per-row outputs, scalars),
+    # (upstream, src, tgt, d_pos, d_neg, neg_idx, row_flags, N, D, mode, margin, dsrc, dtgt),
+    # (feature, T, anchors, nb, C, A, knn, sigma, out, idx, w), (dout, idx, w, nb, C, A, knn, dfeature)
+    _cd = ctypes.c_double
+    lib.epn_triplet_batch_hard_f32.argtypes = [_vp, _vp, _ci, _ci, _ci, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.epn_triplet_batch_hard_bwd_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cd, _vp, _vp, _vp]
+    lib.epn_anchor_interp_f32.argtypes = [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _cd, _vp, _vp, _vp, _vp]
+    lib.epn_anchor_interp_bwd_f32.argtypes = [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

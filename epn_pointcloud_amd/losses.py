@@ -1,0 +1,191 @@
+"""The descriptor network's training loss on the GPU: batch-hard triplet mining over two descriptor sets and the anchor
+interpolation of the equivariance term, the two pieces of the reference's TripletBatchLoss (vgtk/vgtk/loss.py:220-235, :280-318,
+:400-445) -- the only loss SPConvNets/trainer_3dmatch.py uses.  The mirror of that class is epn_pointcloud_amd.vgtk.loss.
+
+Specification: include/epn_so3conv.h (epn_triplet_batch_hard_f32 and its backward, epn_anchor_interp_f32 and its backward) and
+DESIGN.md 3.1d; kernels: csrc/triplet_loss.hip.  Forward two launches (one for the interpolation), backward one; nothing
+synchronises with the host and nothing indexes with a boolean mask, so a step that ends in this loss can be captured into a
+HIP graph -- the reference's dist_mat[is_neg] (loss.py:234) cannot.
+
+Shapes and dtypes are checked on the host before the device is touched: type, shape, dtype, then device."""
+import collections
+
+import torch
+
+from . import _lib
+
+MODES = {"hard": 0, "soft": 1, "contrastive": 2}        # the mode numbers of include/epn_so3conv.h
+EPS = 1e-6                                              # pairwise_distance_matrix's clamp, loss.py:220
+MAX_ROWS = 65536
+ANCHOR_COUNTS = (12, 60)
+KNN = 3
+
+TripletResult = collections.namedtuple("TripletResult", "loss accuracy pos neg neg_idx nn_idx")
+TripletResult.__doc__ = """batch_hard_triplet's result: loss (f32 scalar, the mean row loss; the only differentiable field),
+accuracy (share of rows whose nearest tgt row is their own), pos and neg (mean positive and mean hardest-negative distance) --
+the four values TripletBatchLoss._forward_invariance returns -- and neg_idx, nn_idx int32 [N]: the hardest negative and the
+nearest tgt row of every src row (the lowest index on a tie)."""
+
+
+def _check_pair(src, tgt, mode, margin):
+    """Everything batch_hard_triplet refuses, decided on the host from metadata alone -> (N, D, mode number)."""
+    for name, t in (("src", src), ("tgt", tgt)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dim() != 2:
+            raise ValueError(f"{name} must be [N, D], got {tuple(t.shape)}")
+    if src.shape != tgt.shape:
+        raise ValueError(f"src {tuple(src.shape)} and tgt {tuple(tgt.shape)} differ in shape: row i of tgt is the positive of row i of src")
+    N, D = src.shape
+    if N < 2:
+        raise ValueError(f"batch-hard mining needs N >= 2 rows, got {N}: with one row there is no negative to mine (the reference "
+                         "fails on it too)")
+    if N > MAX_ROWS:
+        raise ValueError(f"N = {N} is beyond the {MAX_ROWS} rows one call takes")
+    if D < 1 or N * D >= 2 ** 31:
+        raise ValueError(f"D must be >= 1 with N * D < 2^31, got N = {N}, D = {D}")
+    for name, t in (("src", src), ("tgt", tgt)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    margin = float(margin)
+    if margin != margin or margin in (float("inf"), float("-inf")) or (mode == "soft" and margin <= 0.0):
+        raise ValueError(f"margin must be finite (and > 0 in soft mode, where it is softplus's beta), got {margin}")
+    for name, t in (("src", src), ("tgt", tgt)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+    _lib.same_device(src, tgt)
+    return N, D, MODES[mode]
+
+
+class _BatchHard(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, tgt, mode, margin):
+        N, D = src.shape
+        src, tgt = src.contiguous(), tgt.contiguous()
+        f32, i32 = dict(dtype=torch.float32, device=src.device), dict(dtype=torch.int32, device=src.device)
+        d_pos, d_neg, row_loss = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(N, **f32)
+        neg_idx, nn_idx, row_flags = torch.empty(N, **i32), torch.empty(N, **i32), torch.empty(N, **i32)
+        scalars = torch.empty(4, **f32)
+        p = _lib.dev_ptr
+        _lib.check(_lib.get_lib().epn_triplet_batch_hard_f32(
+            p(src, "src"), p(tgt, "tgt"), N, D, mode, margin, EPS, p(d_pos, "d_pos"), p(d_neg, "d_neg"), p(row_loss, "row_loss"),
+            p(neg_idx, "neg_idx", torch.int32), p(nn_idx, "nn_idx", torch.int32), p(row_flags, "row_flags", torch.int32),
+            p(scalars, "scalars"), _lib.stream_of(src)), "triplet_batch_hard")
+        ctx.save_for_backward(src, tgt, d_pos, d_neg, neg_idx, row_flags)
+        ctx.mode, ctx.margin = mode, margin
+        ctx.set_materialize_grads(False)                    # no zero fills for the outputs nobody differentiates
+        loss, accuracy, pos, neg = scalars.unbind(0)
+        ctx.mark_non_differentiable(accuracy, pos, neg, d_pos, d_neg, row_loss, neg_idx, nn_idx, row_flags)
+        return loss, accuracy, pos, neg, d_pos, d_neg, row_loss, neg_idx, nn_idx, row_flags
+
+    @staticmethod
+    def backward(ctx, g_loss, *unused):
+        if g_loss is None:
+            return None, None, None, None
+        src, tgt, d_pos, d_neg, neg_idx, row_flags = ctx.saved_tensors
+        N, D = src.shape
+        upstream = g_loss.reshape(1).to(torch.float32).contiguous()
+        dsrc, dtgt = torch.empty_like(src), torch.empty_like(tgt)
+        p = _lib.dev_ptr
+        _lib.check(_lib.get_lib().epn_triplet_batch_hard_bwd_f32(
+            p(upstream, "upstream"), p(src, "src"), p(tgt, "tgt"), p(d_pos, "d_pos"), p(d_neg, "d_neg"),
+            p(neg_idx, "neg_idx", torch.int32), p(row_flags, "row_flags", torch.int32), N, D, ctx.mode, ctx.margin,
+            p(dsrc, "dsrc"), p(dtgt, "dtgt"), _lib.stream_of(src)), "triplet_batch_hard_bwd")
+        return dsrc, dtgt, None, None
+
+
+def batch_hard_rows(src, tgt, mode="hard", margin=1.0):
+    """batch_hard_triplet with the per-row outputs of the entry as well -> (TripletResult, rows) with rows a dict of d_pos,
+    d_neg, row_loss f32 [N] and row_flags int32 [N] (include/epn_so3conv.h).  None of the per-row tensors is differentiable."""
+    N, D, m = _check_pair(src, tgt, mode, margin)
+    loss, accuracy, pos, neg, d_pos, d_neg, row_loss, neg_idx, nn_idx, row_flags = _BatchHard.apply(src, tgt, m, float(margin))
+    return (TripletResult(loss, accuracy, pos, neg, neg_idx, nn_idx),
+            dict(d_pos=d_pos, d_neg=d_neg, row_loss=row_loss, row_flags=row_flags))
+
+
+def batch_hard_triplet(src, tgt, mode="hard", margin=1.0):
+    """(src, tgt f32 [N,D] on the device: row i of tgt is the positive of row i of src, every other row a negative; mode "hard" |
+    "soft" | "contrastive": relu(pos - neg + margin), softplus(pos - neg, beta=margin), pos + relu(margin - neg)) ->
+    TripletResult.  Distances are sqrt(max(sum_d (s - t)^2, 1e-6)) from the differences in fp64; the hardest negative of a row is
+    its nearest other tgt row.  loss.backward() reaches src and tgt through one launch; accuracy, pos and neg are for logging
+    and carry no gradient."""
+    return batch_hard_rows(src, tgt, mode, margin)[0]
+
+
+def _check_interp(feature, T, anchors, sigma):
+    """Everything interpolate_anchor_features refuses, on the host -> (nb, C, A)."""
+    for name, t in (("feature", feature), ("T", T), ("anchors", anchors)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if anchors.dim() != 3 or tuple(anchors.shape[1:]) != (3, 3):
+        raise ValueError(f"anchors must be [A, 3, 3], got {tuple(anchors.shape)}")
+    A = anchors.shape[0]
+    if A not in ANCHOR_COUNTS:
+        raise ValueError(f"the anchor interpolation takes A in {ANCHOR_COUNTS} anchors (the tetrahedral and icosahedral tables), got {A}")
+    if feature.dim() != 3 or feature.shape[2] != A or feature.shape[1] < 1:
+        raise ValueError(f"feature must be [nb, C, {A}] with C >= 1, got {tuple(feature.shape)}")
+    nb, C = feature.shape[0], feature.shape[1]
+    if T.dim() != 3 or T.shape[0] != nb or tuple(T.shape[1:]) not in ((3, 3), (4, 4)):
+        raise ValueError(f"T must be [{nb}, 3, 3] or [{nb}, 4, 4], got {tuple(T.shape)}")
+    if nb * C * A >= 2 ** 31:
+        raise ValueError(f"feature has {nb * C * A} elements, one call takes fewer than 2^31")
+    for name, t in (("feature", feature), ("T", T), ("anchors", anchors)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    sigma = float(sigma)
+    if not 0.0 < sigma < float("inf"):
+        raise ValueError(f"sigma must be finite and > 0, got {sigma}")
+    for name, t in (("feature", feature), ("T", T), ("anchors", anchors)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+    _lib.same_device(feature, T, anchors)
+    return nb, C, A
+
+
+class _AnchorInterp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feature, R, anchors, sigma):
+        nb, C, A = feature.shape
+        feature = feature.contiguous()
+        out = torch.empty_like(feature)
+        idx = torch.empty((nb, A, KNN), dtype=torch.int32, device=feature.device)
+        w = torch.empty((nb, A, KNN), dtype=torch.float32, device=feature.device)
+        p = _lib.dev_ptr
+        if nb > 0:
+            _lib.check(_lib.get_lib().epn_anchor_interp_f32(
+                p(feature, "feature"), p(R, "T"), p(anchors, "anchors"), nb, C, A, KNN, sigma, p(out, "out"),
+                p(idx, "idx", torch.int32), p(w, "w"), _lib.stream_of(feature)), "anchor_interp")
+        ctx.save_for_backward(idx, w)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(idx, w)
+        return out, idx, w
+
+    @staticmethod
+    def backward(ctx, g_out, *unused):
+        if g_out is None:
+            return None, None, None, None
+        idx, w = ctx.saved_tensors
+        g_out = g_out.to(torch.float32).contiguous()
+        nb, C, A = g_out.shape
+        dfeature = torch.empty_like(g_out)
+        p = _lib.dev_ptr
+        if nb > 0:
+            _lib.check(_lib.get_lib().epn_anchor_interp_bwd_f32(
+                p(g_out, "dout"), p(idx, "idx", torch.int32), p(w, "w"), nb, C, A, KNN, p(dfeature, "dfeature"),
+                _lib.stream_of(g_out)), "anchor_interp_bwd")
+        return dfeature, None, None, None
+
+
+def interpolate_anchor_features(feature, T, anchors, sigma=0.2, return_weights=False):
+    """(feature f32 [nb,C,A]: per-anchor features; T f32 [nb,3,3] or [nb,4,4]: the rigid transform of every sample, of which
+    the rotation block is used; anchors f32 [A,3,3], A = 12 or 60) -> f32 [nb,C,A]: for every sample b and anchor n the blend of
+    the features at the three anchors m with the largest tr(T_b^T A_n A_m^T), weighted by the softmax of those traces over
+    sigma.  TripletBatchLoss._interpolate (loss.py:400-445) with the gather done PER SAMPLE -- the reference's line :424 indexes
+    the anchor axis of every sample with the indices of all samples and fails for nb >= 2.  The gradient reaches feature only.
+    return_weights=True -> (out, idx int32 [nb,A,3], w f32 [nb,A,3])."""
+    _check_interp(feature, T, anchors, sigma)
+    R = T[:, :3, :3].detach().contiguous()
+    out, idx, w = _AnchorInterp.apply(feature, R, anchors.detach().contiguous(), float(sigma))
+    return (out, idx, w) if return_weights else out

@@ -1,0 +1,73 @@
+"""Mirror of vgtk/vgtk/loss.py:TripletBatchLoss (:239-445), the loss SPConvNets/trainer_3dmatch.py trains the descriptor network
+with, on the kernels of csrc/triplet_loss.hip (epn_pointcloud_amd.losses; include/epn_so3conv.h).
+
+Same constructor, same forward signature, same return shapes.  What differs, on purpose:
+  * Distances come from the differences in fp64, not from |x|^2 + |y|^2 - 2 x.y in fp32; equal in exact arithmetic, closer to
+    it in practice (the expansion cancels on the positives).
+  * Nothing synchronises with the host (the reference's dist_mat[is_neg], loss.py:234, does), so forward + backward can be
+    captured into a HIP graph.
+  * The equivariance term gathers per sample.  The reference's _interpolate (loss.py:423-424) flattens the neighbour indices of
+    ALL samples and applies them to the anchor axis of EVERY sample, which raises for every batch larger than one; the
+    commented-out batched_index_select beside it (:427) is what is implemented here.
+  * accuracy, pos and neg are logging values without a gradient (upstream they are differentiable in principle and never
+    differentiated).
+  * Debug attributes: match_idx [N,1], fpos [N] and cneg [N] are kept; all_dist is NOT, because the N x N matrix is never
+    formed; gt_idx (upstream builds arange(N) on opt.device in every forward, to compare with its top-1 indices) is NOT either:
+    the kernel counts nn_idx[i] == i itself, and opt.device is read only if present.
+  * _forward_attention is left out: upstream it raises for every loss type except 'no_reg', its entropy term never enters
+    the loss, and forward() never calls it."""
+import torch
+import torch.nn as nn
+
+from .. import losses
+
+
+class TripletBatchLoss(nn.Module):
+    def __init__(self, opt, anchors, sigma=2e-1, interpolation='spherical', alpha=0.0):
+        """anchors f32 [A,3,3] (A = 12 or 60): the rotation table of the network, kept as a buffer.  opt.train_loss.loss_type is
+        "hard", "soft" or "contrastive"; opt.train_loss.margin the hinge margin (in "soft" mode softplus's beta).  sigma divides
+        the traces in the softmax over the three nearest anchors; alpha weighs the equivariance term; interpolation is accepted
+        for the signature only (upstream reads it nowhere)."""
+        super(TripletBatchLoss, self).__init__()
+        self.register_buffer('anchors', anchors)
+        self.device = getattr(opt, 'device', None)
+        self.loss = opt.train_loss.loss_type
+        self.margin = opt.train_loss.margin
+        if self.loss not in losses.MODES:
+            raise ValueError(f"opt.train_loss.loss_type must be one of {sorted(losses.MODES)}, got {self.loss!r}")
+        self.alpha = alpha
+        self.sigma = sigma
+        self.interpolation = interpolation
+        self.k_precision = 1
+        self.iter_counter = 0
+
+    def forward(self, src, tgt, T, equi_src=None, equi_tgt=None):
+        if self.alpha > 0 and equi_src is not None and equi_tgt is not None:
+            return self._forward_equivariance(src, tgt, equi_src, equi_tgt, T)
+        else:
+            return self._forward_invariance(src, tgt)
+
+    def _forward_invariance(self, src, tgt):
+        """(src, tgt f32 [N,D]: descriptors, row i of tgt the positive of row i of src) -> (loss, accuracy, mean positive distance,
+        mean hardest-negative distance)."""
+        r, rows = losses.batch_hard_rows(src, tgt, self.loss, self.margin)
+        # what upstream leaves on the module for inspection, minus all_dist
+        self.match_idx = r.nn_idx.unsqueeze(1)
+        self.fpos = rows["d_pos"]
+        self.cneg = rows["d_neg"]
+        return r.loss, r.accuracy, r.pos, r.neg
+
+    def _forward_equivariance(self, src, tgt, equi_src, equi_tgt, T):
+        inv = self._forward_invariance(src, tgt)
+        n = src.shape[0]
+        # [N,C,A] per-anchor features: the target side is resampled on the source's anchors (per sample), then both are flattened
+        flat_tgt = self._interpolate(equi_tgt, T, sigma=self.sigma).reshape(n, -1)
+        equi = losses.batch_hard_triplet(equi_src.reshape(n, -1), flat_tgt, self.loss, self.margin)
+        return inv[0] + self.alpha * equi.loss, list(inv), [equi.loss, equi.accuracy, equi.pos, equi.neg]
+
+    def _interpolate(self, feature, T, knn=3, sigma=1e-1):
+        """(feature f32 [N,C,A], T f32 [N,4,4] or [N,3,3]) -> f32 [N,C,A]: losses.interpolate_anchor_features with this module's
+        anchors; knn must be 3."""
+        if knn != losses.KNN:
+            raise ValueError(f"the anchor interpolation blends {losses.KNN} neighbours, got knn = {knn}")
+        return losses.interpolate_anchor_features(feature, T, self.anchors, sigma)

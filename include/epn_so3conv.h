@@ -295,6 +295,70 @@ int epn_rotation_decode_f32(const float *wts, const float *y, const float *ancho
                             int b, int A, int nr, float *pred_R, int32_t *preds, float *conf, float *margin, float *pred_Rs,
                             int32_t *hits, float *err, epn_stream_t stream);
 
+/* The descriptor network's training loss: batch-hard triplet mining and the anchor interpolation of its equivariance term
+ * (csrc/triplet_loss.hip).  All tensors are contiguous device memory, float or int32.  Arithmetic is fp64 on
+ * the fp32 inputs and every output is rounded once to fp32.  No workspace, no atomics, no host synchronisation (the calls can
+ * be captured into a HIP graph); every sum runs in a fixed order, so two runs are bitwise equal.  The N x N distance matrix is
+ * never written.
+ * Refusals, decided before any HIP runtime call: EPN_EINVAL for N outside 2..65536 (the reference's mining fails on N = 1 too:
+ * there is no negative), D < 1, N * D >= 2^31, an unknown mode, eps <= 0, a non-finite margin (soft: margin <= 0), C < 1,
+ * A not 12 or 60, knn != 3, nb < 0, nb * C * A >= 2^31, sigma <= 0; nb == 0 succeeds and launches nothing; then EPN_ENULL for
+ * a pointer that is NULL (all are required).
+ *
+ * epn_triplet_batch_hard_f32 (pairwise_distance_matrix, batch_hard_negative_mining and
+ *   TripletBatchLoss._forward_invariance, vgtk/vgtk/loss.py:220-235 and :280-318): src, tgt f32[N,D]; mode one of
+ *   EPN_TRIPLET_*; margin; eps (the reference's 1e-6).
+ *     d2(i,j)   = sum_d (src[i,d] - tgt[j,d])^2: the difference formed in fp64, the terms added in ascending d with one fused
+ *                 multiply-add each.  Equal in exact arithmetic to the reference's |x|^2 + |y|^2 - 2 x.y, without the
+ *                 cancellation that form suffers where unit descriptors are close.
+ *     dist(i,j) = sqrt(d2 < eps ? eps : d2)
+ *     d_pos[i]  = dist(i,i);  d_neg[i] = min over j != i of dist(i,j), neg_idx[i] the lowest such j;
+ *     nn_idx[i] = the lowest j with the smallest dist(i,j) over all j
+ *     row_loss  hard: max(d_pos - d_neg + margin, 0);  soft: x = d_pos - d_neg, x if margin x > 20, else
+ *               log1p(exp(margin x)) / margin (torch's softplus with beta = margin);  contrastive: d_pos + max(margin - d_neg, 0)
+ *     row_flags bit 0: d2(i,i) < eps; bit 1: d2(i,neg_idx[i]) < eps; bit 2: the hinge is active (hard: d_pos - d_neg + margin
+ *               > 0; contrastive: margin - d_neg > 0; soft: always set) -- decided on the unrounded values
+ *   -> d_pos, d_neg, row_loss f32[N], neg_idx, nn_idx, row_flags i32[N] (outputs, not scratch: the backward reads them and they
+ *   are what makes the entry testable) and scalars f32[4] = mean row_loss, #{i: nn_idx[i] == i} / N, mean d_pos, mean d_neg,
+ *   each the fp64 mean of the ROUNDED per-row outputs (thread t adds rows t, t + 256, ... ascending, then a fixed tree),
+ *   rounded once.  Two launches.  neg_idx and nn_idx lie in 0..N-1 and neg_idx[i] != i for any input, NaN included.
+ *
+ * epn_triplet_batch_hard_bwd_f32: upstream f32[1] (the gradient of scalars[0], on the device), src, tgt and the per-row outputs
+ *   above -> dsrc, dtgt f32[N,D], every element written.  With x = d_pos - d_neg,
+ *     hard: gp = gn = bit 2;  soft: gp = gn = 1 if margin x > 20, else 1 / (1 + exp(-margin x));  contrastive: gp = 1, gn = bit 2
+ *     cp[i] = bit 0 ? 0 : upstream gp / (N d_pos[i]);  cn[i] = bit 1 ? 0 : upstream gn / (N d_neg[i])
+ *     dsrc[i] = cp[i] (src[i] - tgt[i]) - cn[i] (src[i] - tgt[neg_idx[i]])
+ *     dtgt[j] = -cp[j] (src[j] - tgt[j]) + sum over the i with neg_idx[i] == j, in ascending i, of cn[i] (src[i] - tgt[j])
+ *   (a clamped distance and an inactive hinge give zero, as torch.clamp and relu do).  dtgt is a gather: the workgroup of row
+ *   j scans neg_idx[0..N).  A neg_idx entry outside 0..N-1 is never used as an address (its row contributes no negative
+ *   term).  One launch.
+ *
+ * epn_anchor_interp_f32 (TripletBatchLoss._interpolate and _rotation_distance, loss.py:400-445, gathering per sample as the
+ *   commented-out line :427 intends; the reference's own line :424 fails for nb >= 2): feature f32[nb,C,A], T f32[nb,3,3],
+ *   anchors f32[A,3,3], A = 12 or 60, knn = 3, sigma > 0.  Per sample b and anchor n:
+ *     trace[m]  = tr(T_b^T A_n A_m^T), P = T_b^T A_n in fp64, then the nine products added in row-major order
+ *     idx[n,0..2] = the three m with the largest trace in descending order, the lower m first on a tie
+ *     w[n,k]    = exp((trace_k - trace_0) / sigma) / sum_k exp((trace_k - trace_0) / sigma)
+ *     out[b,c,n] = sum_k w[n,k] feature[b,c,idx[n,k]] (k ascending, unrounded w)
+ *   -> out f32[nb,C,A], idx i32[nb,A,3], w f32[nb,A,3].  idx lies in 0..A-1 for any input.  One launch, one workgroup per sample.
+ *
+ * epn_anchor_interp_bwd_f32: dout f32[nb,C,A], idx, w as written above -> dfeature f32[nb,C,A], every element written:
+ *     dfeature[b,c,m] = sum over the entries (n,k) with idx[n,k] == m, in ascending 3 n + k, of w[n,k] dout[b,c,n]
+ *   a gather over the 3 A saved entries (idx is only compared, never an address).  T gets no gradient.  One launch. */
+#define EPN_TRIPLET_HARD 0
+#define EPN_TRIPLET_SOFT 1
+#define EPN_TRIPLET_CONTRASTIVE 2
+int epn_triplet_batch_hard_f32(const float *src, const float *tgt, int N, int D, int mode, double margin, double eps,
+                               float *d_pos, float *d_neg, float *row_loss, int32_t *neg_idx, int32_t *nn_idx,
+                               int32_t *row_flags, float *scalars, epn_stream_t stream);
+int epn_triplet_batch_hard_bwd_f32(const float *upstream, const float *src, const float *tgt, const float *d_pos,
+                                   const float *d_neg, const int32_t *neg_idx, const int32_t *row_flags, int N, int D, int mode,
+                                   double margin, float *dsrc, float *dtgt, epn_stream_t stream);
+int epn_anchor_interp_f32(const float *feature, const float *T, const float *anchors, int nb, int C, int A, int knn, double sigma,
+                          float *out, int32_t *idx, float *w, epn_stream_t stream);
+int epn_anchor_interp_bwd_f32(const float *dout, const int32_t *idx, const float *w, int nb, int C, int A, int knn,
+                              float *dfeature, epn_stream_t stream);
+
 /* ------------------------------------------------------------------ InterSO3Conv ------------ */
 
 /* Geometry + shapes of one inter convolution (vgtk/vgtk/so3conv/functional.py:118-178).
