@@ -1,5 +1,9 @@
 // Internal interface of the GEMM translation units (the BasicSO3Conv weight contractions as MFMA GEMMs): gemm.hip (NT, casts),
-// gemm_tn.hip (TN weight gradients), gemm_x3.hip / gemm_pp.hip (split forms), and the device parts they share.
+// gemm_tn.hip (TN weight gradients), gemm_x3.hip / gemm_pp.hip (split forms), and the parts they share.  Host side of the NT
+// family: nt_marshal / nt_for_chunks (entry-point problems -> GemmNtBatch, six at a time) and nt_plan_tiles (the tile plan of a
+// grouped launch) live here; the instance tables and selection rules are in gemm.hip (EPN_NT_INSTANCES, nt_choose) and
+// gemm_x3.hip (EPN_X3_INSTANCES, x3_choose).  Device side: the vector types, the operand splits, the MFMA term groups, the
+// epilogue by-products and the statement macros EPN_NT_DECODE / EPN_NT_STORE the NT kernel bodies share.
 #pragma once
 #include "epn_common.h"
 
@@ -25,6 +29,59 @@ struct GemmNtBatch {
     unsigned ntiles;
     GemmNtProb p[GEMM_MAX_PROB];
 };
+
+
+// entry-point problems i0 .. i0 + 5 of `probs` -> one launcher batch, every field set (tiles: nt_plan_tiles; Bp / b_amax: the
+// split launcher); a_amax: the two-piece entry's device maxima per problem, or nullptr
+inline GemmNtBatch nt_marshal(const epn_gemm_nt_problem *probs, int nprob, int i0, const float *const *a_amax) {
+    GemmNtBatch B{};
+    B.nprob = nprob - i0 < GEMM_MAX_PROB ? nprob - i0 : GEMM_MAX_PROB;
+    for (int i = 0; i < B.nprob; ++i) {
+        const epn_gemm_nt_problem &q = probs[i0 + i];
+        GemmNtProb &p = B.p[i];
+        p.A = q.A; p.Bt = q.Bt; p.C = q.C; p.M = q.M; p.N = q.N; p.K = q.K; p.lda = q.lda; p.ldb = q.ldb; p.ldc = q.ldc;
+        p.stats = q.col_stats; p.c_amax = reinterpret_cast<unsigned *>(q.c_amax);
+        p.a_amax = a_amax ? a_amax[i0 + i] : nullptr;
+    }
+    return B;
+}
+// the chunk loop of the NT entry points: one grouped launch per GEMM_MAX_PROB problems, launch(B) != 0 ends the call
+template <typename F>
+int nt_for_chunks(int nprob, const epn_gemm_nt_problem *probs, const float *const *a_amax, F launch) {
+    if (!probs) return EPN_ENULL;
+    if (nprob < 1) return EPN_EINVAL;
+    for (int i0 = 0; i0 < nprob; i0 += GEMM_MAX_PROB) {
+        GemmNtBatch B = nt_marshal(probs, nprob, i0, a_amax);
+        const int rc = launch(B);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// Tile plan of a grouped NT launch with BM x BN block tiles: orders the problems, fills tiles_n / tile0 / ntile and B.ntiles
+// (= the grid; 0: every problem is empty, nothing to launch).
+// Workgroup -> problem by launch order, then the XCD-aware remap WITHIN the problem (every problem's first
+// workgroup is a multiple of 8, so workgroup % 8 = XCD holds locally too): each XCD gets a contiguous range of
+// every problem's tiles.  One remap over the whole table gave XCD 0 all tiles of the longest-K problem and XCD 7 the
+// short ones -- a grouped launch ran 10 % slower than its problems launched one by one.
+inline unsigned nt_plan_tiles(GemmNtBatch &B, int BM, int BN) {
+    // longest contraction first: the tiles are dispatched in table order, and a tile's run time is ~K, so the short
+    // tiles of the other problems fill the last round (the spectral blocks of a layer have K = d*c, d = 1..5)
+    for (int i = 1; i < B.nprob; ++i)
+        for (int k = i; k > 0 && B.p[k].K > B.p[k - 1].K; --k) {
+            const GemmNtProb tmp = B.p[k]; B.p[k] = B.p[k - 1]; B.p[k - 1] = tmp;
+        }
+    unsigned total = 0;
+    for (int i = 0; i < B.nprob; ++i) {
+        GemmNtProb &p = B.p[i];
+        p.tiles_n = (p.N + BN - 1) / BN;
+        p.tile0 = total;
+        p.ntile = (unsigned)((p.M + BM - 1) / BM) * p.tiles_n;
+        total += i + 1 < B.nprob ? (p.ntile + 7u) & ~7u : p.ntile;
+    }
+    B.ntiles = total;
+    return total;
+}
 
 struct GemmTnArgs {        // C[N1][N2] = X[R][N1]^T . Y[R][N2]
     const void *X, *Y;
@@ -63,8 +120,17 @@ template <> struct ElemOf<__bf16> { static constexpr int PER16 = 8; };
 __device__ __forceinline__ void glds16(const void *g, char *lds_wave_base) {
     __builtin_amdgcn_global_load_lds((glb_void *)g, (lds_void *)lds_wave_base, 16, 0, 0);
 }
-__device__ __forceinline__ void glds16_nt(const void *g, char *lds_wave_base) {      // non-temporal: a stream read once
-    __builtin_amdgcn_global_load_lds((glb_void *)g, (lds_void *)lds_wave_base, 16, 0, 2);
+
+// maxima of |x| as bit patterns of non-negative floats (unsigned order = float order): the largest over the 64 lanes of a wave
+// (every lane gets it), and the running maximum raised by one value -- `bits` with any sign; non-finite values are left out
+#define EPN_WAVE_UMAX(m_)                                                                       \
+    _Pragma("unroll") for (int o = 32; o >= 1; o >>= 1) {                                        \
+        const unsigned v = (unsigned)__shfl_xor((int)(m_), o, 64);                               \
+        (m_) = v > (m_) ? v : (m_);                                                              \
+    }
+__device__ __forceinline__ unsigned absmax_finite(unsigned m, unsigned bits) {
+    const unsigned a = bits & 0x7fffffffu;
+    return (a > m && a < 0x7f800000u) ? a : m;
 }
 
 // lossless split of fp32 into three bf16 pieces x = h + m + l (gemm_x3.hip): pairs packed as v_cvt_pk_bf16_f32 leaves them
@@ -86,6 +152,17 @@ __device__ __forceinline__ void split3(const float (&x)[8], bf16x8 &h, bf16x8 &m
     }
     h = __builtin_bit_cast(bf16x8, H); m = __builtin_bit_cast(bf16x8, M); l = __builtin_bit_cast(bf16x8, L);
 }
+// one pair -> one packed dword per plane: planes[q * plane_stride + offset], q = 0 (h), 1 (m), 2 (l)
+#define EPN_SPLIT3_PAIR_STORE(x0_, x1_, planes_, plane_stride_, offset_)                        \
+    do {                                                                                         \
+        const float sx0 = (x0_), sx1 = (x1_);                                                    \
+        const unsigned hp = pack_rne(sx0, sx1);                                                  \
+        const float r0 = sx0 - lo_f(hp), r1 = sx1 - hi_f(hp);                                    \
+        const unsigned mp = pack_rne(r0, r1);                                                    \
+        (planes_)[offset_] = hp;                                                                 \
+        (planes_)[(plane_stride_) + (offset_)] = mp;                                             \
+        (planes_)[2 * (plane_stride_) + (offset_)] = pack_rne(r0 - lo_f(mp), r1 - hi_f(mp));     \
+    } while (0)
 
 // ---- two-piece fp16 split ("f16x2", round 5): x 2^s = h + l with h = rne_f16(x 2^s), l = rne_f16(x 2^s - h) keeps 22-23
 // significant bits of every element within 2^-17 of the tensor's largest magnitude (absolute error <= max|x| 2^-39 below
@@ -208,6 +285,45 @@ __device__ __forceinline__ float f2_unscale(gemm_f32x16 (&acc)[TM][TN], float ux
     return chk;
 }
 
+// ---- text the NT kernel bodies share (gemm_nt_kernel, gemm_nt_x3_kernel, gemm_nt_pp_kernel / gemm_nt_pp2_kernel): statement
+// macros expanded in the kernel's scope (TM, TN, BM, BN; the store also reads P, m0, n0, wm, wn, li, lj, acc).  As inlined
+// functions each of them changed the instruction streams of some instances (CHANGELOG: the table of forms tried).
+// which problem / tile of the grouped launch B_ this workgroup computes (the plan: nt_plan_tiles above): defines P, t, m0, n0;
+// a padding workgroup between two problems ENDS here
+#define EPN_NT_DECODE(B_)                                                                                            \
+    int pi = 0;                                                                                                      \
+    _Pragma("unroll") for (int i = 1; i < GEMM_MAX_PROB; ++i)                                                        \
+        if (i < (B_).nprob && blockIdx.x >= (B_).p[i].tile0) pi = i;                                                 \
+    const GemmNtProb &P = (B_).p[pi];                                                                                \
+    if (blockIdx.x - P.tile0 >= P.ntile) return;                                                                     \
+    const unsigned t = epn_xcd_tile(blockIdx.x - P.tile0, P.ntile);                                                  \
+    const long long m0 = (long long)(t / P.tiles_n) * BM;                                                            \
+    const int n0 = (int)(t % P.tiles_n) * BN;
+#define EPN_NT_ZERO_ACC(acc_)                                                                   \
+    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) (acc_)[i][j][r] = 0.f;
+// epilogue store of a wave's TM x TN tiles of `acc` to C_ (TO_ *): D[row = (r&3) + 8 (r>>2) + 4 lj][col = li]; ENDS the kernel.
+// Interior tiles first, then the checked form (why: gemm_nt_kernel, which keeps its own copy -- it stores through store_out,
+// and the same stores written either way schedule differently).  The split-form kernels' epilogue (gemm_x3.hip, gemm_pp.hip).
+#define EPN_NT_STORE_TILE(TO_, C_)                                                                                   \
+    if (m0 + BM <= P.M && n0 + BN <= P.N && (long long)BM * P.ldc < (1LL << 30)) {                                   \
+        TO_ *__restrict__ cw = (C_) + (size_t)(m0 + wm * TM * 32) * P.ldc + (n0 + wn * TN * 32);                     \
+        const unsigned ldc = (unsigned)P.ldc;                                                                        \
+        const unsigned lane_off = 4u * lj * ldc + li;                                                                \
+        _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int r = 0; r < 16; ++r) {              \
+            const unsigned o = lane_off + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldc;                         \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j) cw[o + j * 32] = (TO_)acc[i][j][r];                       \
+        }                                                                                                            \
+        return;                                                                                                      \
+    }                                                                                                                \
+    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) {                  \
+        const int n = n0 + (wn * TN + j) * 32 + li;                                                                  \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                             \
+            const long long m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lj;                           \
+            if (m < P.M && n < P.N) (C_)[m * P.ldc + n] = (TO_)acc[i][j][r];                                         \
+        }                                                                                                            \
+    }
+
 // Column statistics of an NT tile, taken from the accumulators in the epilogue (the per-channel sums a following
 // BatchNorm / InstanceNorm needs: SURVEY 8f.1 -- no separate pass over C).  acc[i][j]: 32 x 32 MFMA tile i (rows) x j
 // (columns) of the wave, D[row = (r&3) + 8 (r>>2) + 4 lj][col = li]; part[(row / 32)][n][2].  The sums are those of the
@@ -260,11 +376,7 @@ __device__ __forceinline__ void nt_c_amax(const gemm_f32x16 (&acc)[TM][TN], unsi
     if constexpr (sizeof(TO) == 2) mf = (float)(__bf16)mf;      // rounding is monotonic: max of the rounded values = the rounded max
     unsigned m = __builtin_bit_cast(unsigned, mf);
     m = m < 0x7f800000u ? m : 0u;                               // (an infinite element: left out, as launch_absmax does; its consumer's own check reports it)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned v = (unsigned)__shfl_xor((int)m, o, 64);
-        m = v > m ? v : m;
-    }
+    EPN_WAVE_UMAX(m)
     if ((threadIdx.x & 63) == 0 && m > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, m);
 }
 #endif

@@ -4,7 +4,9 @@
 //   NT   C[M][N]   = A[M][K] . Bt[N][K]^T      activation x weight: out = G W^T, dG = dOut (W^T)^T, the spectral blocks
 //   TN   C[N1][N2] = X[R][N1]^T . Y[R][N2]     weight gradients: dW = dOut^T G (contraction over the R = b*p*a columns)
 //
-// This file holds the NT kernel, the generic fallbacks and the cast / transpose kernels; the TN family is gemm_tn.hip.  Both stream 128-byte row segments through a double-buffered LDS ring with direct-to-LDS loads
+// This file holds the NT kernel, its instance table (EPN_NT_INSTANCES) with the selection rule (nt_choose), the generic
+// fallbacks and the cast / transpose kernels; the TN family is gemm_tn.hip, the tile planner and the marshalling of the entry
+// points' problems are in gemm.h (nt_plan_tiles, nt_marshal / nt_for_chunks).  Both stream 128-byte row segments through a double-buffered LDS ring with direct-to-LDS loads
 // (global_load_lds_dwordx4, one 1 KiB wave instruction = 8 row segments), one barrier per K step.  The NT image is
 // XOR-swizzled on the SOURCE address (16-byte slot ^ ((row >> 1) & 7)) so that the ds_read_b128 fragment reads are
 // bank-conflict free (cdna_hip_programming.md T2 / rule 21); the TN image is read along its rows and needs none.
@@ -40,20 +42,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_kernel(GemmNtBatch B) 
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // ---- which problem / tile
-    // Workgroup -> problem by launch order, then the XCD-aware remap WITHIN the problem (every problem's first
-    // workgroup is a multiple of 8, so workgroup % 8 = XCD holds locally too): each XCD gets a contiguous range of
-    // every problem's tiles.  One remap over the whole table gave XCD 0 all tiles of the longest-K problem and XCD 7 the
-    // short ones -- a grouped launch ran 10 % slower than its problems launched one by one.
-    int pi = 0;
-#pragma unroll
-    for (int i = 1; i < GEMM_MAX_PROB; ++i)
-        if (i < B.nprob && blockIdx.x >= B.p[i].tile0) pi = i;
-    const GemmNtProb &P = B.p[pi];
-    if (blockIdx.x - P.tile0 >= P.ntile) return;
-    const unsigned t = epn_xcd_tile(blockIdx.x - P.tile0, P.ntile);
-    const long long m0 = (long long)(t / P.tiles_n) * BM;
-    const int n0 = (int)(t % P.tiles_n) * BN;
+    EPN_NT_DECODE(B)                               // ---- which problem / tile: P, m0, n0 (gemm.h, with the plan it reads)
     const T *__restrict__ A = static_cast<const T *>(P.A);
     const T *__restrict__ Bt = static_cast<const T *>(P.Bt);
     const int nk = P.K / BKE;
@@ -79,9 +68,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_kernel(GemmNtBatch B) 
     auto stage_one = [&](int buf, int i) {
         const int g = wave + i * NW;
         if (NG % NW == 0 || g < NG) {
-#ifdef EPN_NT_NTA
-            if (RPG * g < BM) glds16_nt(src[i], smem + buf * (ROWS * ROWB) + g * 1024); else
-#endif
             glds16(src[i], smem + buf * (ROWS * ROWB) + g * 1024);
             src[i] += BKE;
         }
@@ -104,12 +90,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_kernel(GemmNtBatch B) 
     for (int i = 0; i < TN; ++i) boff[i] = (BM + (wn * TN + i) * 32 + li) * ROWB;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    EPN_NT_ZERO_ACC(acc)
 
     // One barrier per K step.  A direct-to-LDS load costs its wave ~60-180 cycles of issue during which it feeds no MFMA,
     // and the two waves of a SIMD leave the barrier together: issued as one burst (wherever in the step) both waves
@@ -316,35 +297,99 @@ __global__ __launch_bounds__(256) void nt_amax_from_c_kernel(const TO *__restric
         const unsigned a = __builtin_bit_cast(unsigned, (float)C[(i / N) * ldc + i % N]) & 0x7fffffffu;
         m = (a > m && a < 0x7f800000u) ? a : m;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned v = (unsigned)__shfl_xor((int)m, o, 64);
-        m = v > m ? v : m;
-    }
+    EPN_WAVE_UMAX(m)
     if ((threadIdx.x & 63) == 0 && m > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, m);
 }
 template <typename T, typename TO, int WGM, int WGN, int TM, int TN, int KS = 8, int NSTG = 2>
 int launch_nt_cfg(GemmNtBatch &B, hipStream_t st) {
-    constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
-    // longest contraction first: the tiles are dispatched in table order, and a tile's run time is ~K, so the short
-    // tiles of the other problems fill the last round (the spectral blocks of a layer have K = d*c, d = 1..5)
-    for (int i = 1; i < B.nprob; ++i)
-        for (int k = i; k > 0 && B.p[k].K > B.p[k - 1].K; --k) {
-            const GemmNtProb tmp = B.p[k]; B.p[k] = B.p[k - 1]; B.p[k - 1] = tmp;
-        }
-    unsigned total = 0;
-    for (int i = 0; i < B.nprob; ++i) {
-        GemmNtProb &p = B.p[i];
-        p.tiles_n = (p.N + BN - 1) / BN;
-        p.tile0 = total;
-        p.ntile = (unsigned)((p.M + BM - 1) / BM) * p.tiles_n;
-        total += i + 1 < B.nprob ? (p.ntile + 7u) & ~7u : p.ntile;
-    }
-    B.ntiles = total;
+    const unsigned total = nt_plan_tiles(B, WGM * TM * 32, WGN * TN * 32);
     if (total == 0) return 0;
     EPN_LAUNCH((gemm_nt_kernel<T, TO, WGM, WGN, TM, TN, KS, NSTG>), dim3(total), dim3(64 * WGM * WGN), 0, st, B);
     EPN_CHECK_LAUNCH();
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the kernel instances
+// Every gemm_nt_kernel<T, TO, ...> instance the library contains is named ONCE, here, for every operand / output type pair:
+// X(code, WGM, WGN, TM, TN, KS, NSTG); block tile (WGM*TM*32) x (WGN*TN*32); code = policy code of the tuning override
+// (tools/gemm_bench.py --cfg), 0 = none.  nt_choose() names a tuple; launch_nt_instance() looks it up and fails with EPN_EINVAL
+// when there is none.  "override only": instantiated, but no rule of nt_choose reaches it for any type (kept: the code object
+// stays what it was).  256 x 64 and 128 x 128 are rule tiles of fp32 only, 256 x 128 (two stages) too: under bf16 operands
+// only the override reaches them.
+#ifdef EPN_TUNING
+// short-K (data-gradient) shapes: four-wave workgroups with 128 accumulators per wave and a half-width K step, so that TWO
+// fit a CU and one's store epilogue overlaps the other's loads (round 6 sweep, tools/r06_dg_sweep.sh ->
+// profiles/r06_bf16_dg_tile_sweep.txt).  MEASURED 25-30 % SLOWER than the 256 x 256 tile on every bf16 data-gradient
+// shape (245760 x 3072 x 256: 0.76-0.79 vs 0.60 ms; hipBLASLt through torch.mm: 0.60-0.62): kept for the record only
+#define EPN_NT_TUNING_INSTANCES(X)                                                                                   \
+    X(7, 2, 2, 2, 4, 4, 2)  /* 128 x 256, 4 waves, K step 32 (bf16) / 16 (fp32), 48 KB */                            \
+    X(8, 2, 2, 4, 2, 4, 2)  /* 256 x 128, 4 waves, same */                                                           \
+    X(10, 2, 2, 2, 4, 8, 2) /* 128 x 256, 4 waves, full K step (96 KB: one workgroup per CU) */
+#else
+#define EPN_NT_TUNING_INSTANCES(X)
+#endif
+#define EPN_NT_INSTANCES(X)                                                                                          \
+    X(0, 8, 1, 2, 1, 4, 2)  /* 512 x  32, half K step */                                                             \
+    X(0, 8, 1, 2, 2, 4, 2)  /* 512 x  64, half K step */                                                             \
+    X(0, 4, 2, 2, 2, 4, 2)  /* 256 x 128, half K step */                                                             \
+    X(0, 8, 1, 2, 1, 8, 2)  /* 512 x  32 */                                                                          \
+    X(0, 8, 1, 2, 2, 8, 2)  /* 512 x  64 */                                                                          \
+    X(1, 4, 2, 2, 2, 8, 2)  /* 256 x 128, 8 waves */                                                                 \
+    X(2, 4, 2, 2, 4, 8, 2)  /* 256 x 256, 8 waves */                                                                 \
+    X(3, 2, 2, 2, 2, 8, 2)  /* 128 x 128, 4 waves (2 workgroups / CU) */                                             \
+    X(4, 2, 4, 2, 2, 8, 2)  /* 128 x 256, 8 waves: override only */                                                  \
+    X(5, 4, 1, 2, 2, 8, 2)  /* 256 x  64, 4 waves */                                                                 \
+    X(6, 2, 2, 4, 2, 8, 2)  /* 256 x 128, 4 waves, 128 x 64 per wave: override only */                               \
+    EPN_NT_TUNING_INSTANCES(X)
+// bf16 operands only (the kernel's static_assert rejects a three-stage ring for fp32 tiles wider than 64)
+#define EPN_NT_BF16_INSTANCES(X) X(0, 4, 2, 2, 2, 8, 3) /* 256 x 128, three stages */
+
+struct NtTile { int wgm, wgn, tm, tn, ks, nstg; };
+
+// The selection rule of the MFMA path.  half_k: some K is a multiple of 4 slots only; M0: rows of problem 0; policy: kernel_policy()
+inline NtTile nt_choose(bool is_fp32, int nprob, int maxn, int minn, bool half_k, long long M0, int policy) {
+    if (half_k) {
+        if (maxn <= 32) return {8, 1, 2, 1, 4, 2};
+        if (maxn <= 64) return {8, 1, 2, 2, 4, 2};
+        return {4, 2, 2, 2, 4, 2};
+    }
+    if ((policy & ~0xff) == 0x100) {           // tuning override (tools/gemm_bench.py --cfg); a code without entry: the rules
+#define EPN_NT_CODE(CODE, ...) if (CODE != 0 && (policy & 0xff) == CODE) return {__VA_ARGS__};
+        EPN_NT_INSTANCES(EPN_NT_CODE)
+#undef EPN_NT_CODE
+    }
+    if (is_fp32 && nprob == 1 && maxn >= 128 && maxn <= 256 && maxn % 128 == 0 && (M0 / 128) * (maxn / 128) >= 3840)
+        // many-tile problems: 128 x 128 tiles, 4 waves, two workgroups per CU (measured on 491520 x 128 and 245760 x 256:
+        // 130-140 TFLOP/s against 124-136 for the 256-row tiles; below ~3840 tiles the big tiles win)
+        return {2, 2, 2, 2, 8, 2};
+    if (is_fp32 && nprob > 1) {
+        // grouped spectral blocks (widths d*c, d = 1, 3, 3, 4, 5): narrow tiles waste less of the ragged widths
+        // (c = 64: 256 x 64 tiles 0.40 ms vs 0.45; c = 128 / 256: 128 x 128 tiles 0.65 / 1.22 vs 0.69 / 1.25, measured)
+        if (maxn <= 320 && minn <= 64) return {4, 1, 2, 2, 8, 2};
+        return {2, 2, 2, 2, 8, 2};
+    }
+    if (maxn <= 32) return {8, 1, 2, 1, 8, 2};      // 512 x 32
+    if (maxn <= 64) return {8, 1, 2, 2, 8, 2};      // 512 x 64
+    // 256 x 256 (fewer LDS fragment reads per MFMA: 6 per 8 instead of 4 per 4).  bf16 too: 11-12 % faster
+    // than the 3-stage 256 x 128 instance on the N >= 256 shapes (245760 x 256 x 6144: 0.92 -> 0.82 ms)
+    if (minn >= 256) return {4, 2, 2, 4, 8, 2};   // (fp32 groups were routed above)
+    // 256 x 128.  bf16 is HBM-bound on these shapes (it streams G or dG): a THREE-stage LDS ring keeps two stages of loads
+    // in flight (144 KB of LDS; the wait before the barrier is vmcnt(loads of one stage), not 0): 10-16 % faster on the
+    // schedule's shapes (245760 x 256 x 6144: 1.07 -> 0.93 ms).  Narrow tiles and fp32 (MFMA-bound) measured no gain.
+    if (!is_fp32) return {4, 2, 2, 2, 8, 3};
+    return {4, 2, 2, 2, 8, 2};
+}
+
+// launches the instance `c` names; EPN_EINVAL when the tables above have none for this type pair
+template <typename T, typename TO>
+int launch_nt_instance(const NtTile &c, GemmNtBatch &B, hipStream_t st) {
+#define EPN_NT_TRY(CODE, WGM, WGN, TM, TN, KS, NSTG)                                                                 \
+    if (c.wgm == WGM && c.wgn == WGN && c.tm == TM && c.tn == TN && c.ks == KS && c.nstg == NSTG)                    \
+        return launch_nt_cfg<T, TO, WGM, WGN, TM, TN, KS, NSTG>(B, st);
+    EPN_NT_INSTANCES(EPN_NT_TRY)
+    if constexpr (sizeof(T) == 2) { EPN_NT_BF16_INSTANCES(EPN_NT_TRY) }
+#undef EPN_NT_TRY
+    return EPN_EINVAL;
 }
 
 template <typename T, typename TO>
@@ -384,53 +429,7 @@ int launch_nt_typed(GemmNtBatch &B, hipStream_t st) {
         }
         return 0;
     }
-    if (half_k) {
-        if (maxn <= 32) return launch_nt_cfg<T, TO, 8, 1, 2, 1, 4>(B, st);
-        if (maxn <= 64) return launch_nt_cfg<T, TO, 8, 1, 2, 2, 4>(B, st);
-        return launch_nt_cfg<T, TO, 4, 2, 2, 2, 4>(B, st);
-    }
-    const int pol = kernel_policy();
-    if ((pol & ~0xff) == 0x100) {           // tuning override (tools/gemm_bench.py --cfg)
-        switch (pol & 0xff) {
-            case 1: return launch_nt_cfg<T, TO, 4, 2, 2, 2>(B, st);      // 256 x 128, 8 waves
-            case 2: return launch_nt_cfg<T, TO, 4, 2, 2, 4>(B, st);      // 256 x 256, 8 waves
-            case 3: return launch_nt_cfg<T, TO, 2, 2, 2, 2>(B, st);      // 128 x 128, 4 waves (2 workgroups / CU)
-            case 4: return launch_nt_cfg<T, TO, 2, 4, 2, 2>(B, st);      // 128 x 256, 8 waves
-            case 5: return launch_nt_cfg<T, TO, 4, 1, 2, 2>(B, st);      // 256 x 64, 4 waves
-            case 6: return launch_nt_cfg<T, TO, 2, 2, 4, 2>(B, st);      // 256 x 128, 4 waves, 128 x 64 per wave
-#ifdef EPN_TUNING
-            // short-K (data-gradient) shapes: four-wave workgroups with 128 accumulators per wave and a half-width K step, so that TWO
-            // fit a CU and one's store epilogue overlaps the other's loads (round 6 sweep, tools/r06_dg_sweep.sh ->
-            // profiles/r06_bf16_dg_tile_sweep.txt).  MEASURED 25-30 % SLOWER than the 256 x 256 tile on every bf16 data-gradient
-            // shape (245760 x 3072 x 256: 0.76-0.79 vs 0.60 ms; hipBLASLt through torch.mm: 0.60-0.62): kept for the record only
-            case 7: return launch_nt_cfg<T, TO, 2, 2, 2, 4, 4, 2>(B, st);   // 128 x 256, 4 waves, K step 32 (bf16) / 16 (fp32), 48 KB
-            case 8: return launch_nt_cfg<T, TO, 2, 2, 4, 2, 4, 2>(B, st);   // 256 x 128, 4 waves, same
-            case 10: return launch_nt_cfg<T, TO, 2, 2, 2, 4, 8, 2>(B, st);  // 128 x 256, 4 waves, full K step (96 KB: one workgroup per CU)
-#endif
-            default: break;
-        }
-    }
-    if (sizeof(T) == 4 && B.nprob == 1 && maxn >= 128 && maxn <= 256 && maxn % 128 == 0 &&
-        (B.p[0].M / 128) * (maxn / 128) >= 3840)
-        // many-tile problems: 128 x 128 tiles, 4 waves, two workgroups per CU (measured on 491520 x 128 and 245760 x 256:
-        // 130-140 TFLOP/s against 124-136 for the 256-row tiles; below ~3840 tiles the big tiles win)
-        return launch_nt_cfg<T, TO, 2, 2, 2, 2>(B, st);
-    if (sizeof(T) == 4 && B.nprob > 1) {
-        // grouped spectral blocks (widths d*c, d = 1, 3, 3, 4, 5): narrow tiles waste less of the ragged widths
-        // (c = 64: 256 x 64 tiles 0.40 ms vs 0.45; c = 128 / 256: 128 x 128 tiles 0.65 / 1.22 vs 0.69 / 1.25, measured)
-        if (maxn <= 320 && minn <= 64) return launch_nt_cfg<T, TO, 4, 1, 2, 2>(B, st);
-        return launch_nt_cfg<T, TO, 2, 2, 2, 2>(B, st);
-    }
-    if (maxn <= 32) return launch_nt_cfg<T, TO, 8, 1, 2, 1>(B, st);      // 512 x 32
-    if (maxn <= 64) return launch_nt_cfg<T, TO, 8, 1, 2, 2>(B, st);      // 512 x 64
-    // 256 x 256 (fewer LDS fragment reads per MFMA: 6 per 8 instead of 4 per 4).  bf16 too: 11-12 % faster
-    // than the 3-stage 256 x 128 instance on the N >= 256 shapes (245760 x 256 x 6144: 0.92 -> 0.82 ms)
-    if (minn >= 256) return launch_nt_cfg<T, TO, 4, 2, 2, 4>(B, st);   // (fp32 groups were routed above)
-    // 256 x 128.  bf16 is HBM-bound on these shapes (it streams G or dG): a THREE-stage LDS ring keeps two stages of loads
-    // in flight (144 KB of LDS; the wait before the barrier is vmcnt(loads of one stage), not 0): 10-16 % faster on the
-    // schedule's shapes (245760 x 256 x 6144: 1.07 -> 0.93 ms).  Narrow tiles and fp32 (MFMA-bound) measured no gain.
-    if constexpr (sizeof(T) == 2) return launch_nt_cfg<T, TO, 4, 2, 2, 2, 8, 3>(B, st);
-    else return launch_nt_cfg<T, TO, 4, 2, 2, 2>(B, st);
+    return launch_nt_instance<T, TO>(nt_choose(sizeof(T) == 4, B.nprob, maxn, minn, half_k, B.p[0].M, kernel_policy()), B, st);
 }
 
 }  // namespace
@@ -493,22 +492,8 @@ int launch_cast_add(const float *src, const void *add_bf16, void *dst_bf16, size
 using namespace epn;
 
 static int nt_entry(int nprob, const epn_gemm_nt_problem *probs, int dtype, int out_dtype, epn_stream_t stream) {
-    if (!probs) return EPN_ENULL;
-    if (nprob < 1) return EPN_EINVAL;
-    hipStream_t st = epn_stream(stream);
-    for (int i0 = 0; i0 < nprob; i0 += GEMM_MAX_PROB) {
-        GemmNtBatch B;
-        B.nprob = nprob - i0 < GEMM_MAX_PROB ? nprob - i0 : GEMM_MAX_PROB;
-        for (int i = 0; i < B.nprob; ++i) {
-            const epn_gemm_nt_problem &q = probs[i0 + i];
-            GemmNtProb &p = B.p[i];
-            p.A = q.A; p.Bt = q.Bt; p.C = q.C; p.M = q.M; p.N = q.N; p.K = q.K; p.lda = q.lda; p.ldb = q.ldb; p.ldc = q.ldc;
-            p.tiles_n = 0; p.tile0 = 0; p.stats = q.col_stats; p.c_amax = reinterpret_cast<unsigned *>(q.c_amax); p.a_amax = p.b_amax = nullptr;
-        }
-        int rc = launch_gemm_nt(B, dtype, out_dtype, st);
-        if (rc) return rc;
-    }
-    return 0;
+    return nt_for_chunks(nprob, probs, nullptr,
+                         [&](GemmNtBatch &B) { return launch_gemm_nt(B, dtype, out_dtype, epn_stream(stream)); });
 }
 
 extern "C" int epn_gemm_nt_f32(int nprob, const epn_gemm_nt_problem *probs, epn_stream_t stream) {

@@ -34,14 +34,9 @@ __global__ void pp_split_kernel(const float *__restrict__ src, long long ld, lon
     const long long r = i / k2;
     const int k = 2 * (int)(i % k2);
     const float x0 = src[r * ld + k], x1 = src[r * ld + k + 1];
-    const unsigned hp = pack_rne(x0, x1);
-    const float r0 = x0 - lo_f(hp), r1 = x1 - hi_f(hp);
-    const unsigned mp = pack_rne(r0, r1);
     const size_t plane = (size_t)rows * k2;
     const size_t o = layout == 0 ? (size_t)i : (((size_t)(k / KS) * rows + r) * KS + (k % KS)) >> 1;
-    planes[o] = hp;
-    planes[plane + o] = mp;
-    planes[2 * plane + o] = pack_rne(r0 - lo_f(mp), r1 - hi_f(mp));
+    EPN_SPLIT3_PAIR_STORE(x0, x1, planes, plane, o);
 }
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -130,12 +125,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_pp2_kernel(PPArgs P, u
     for (int i = 0; i < TN; ++i) boff[i] = 2 * PA + ((wn * TN + i) * 32 + li) * ROWB;
     const int fsw = (li >> 2) & 3;
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    EPN_NT_ZERO_ACC(acc)
 #pragma unroll
     for (int s = 0; s < NSTG - 1; ++s)
         if (s < nk) stage(s);
@@ -261,12 +251,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_pp_kernel(PPArgs P, un
     const int fsw = (li >> 2) & 3;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    EPN_NT_ZERO_ACC(acc)
 
 #pragma unroll
     for (int s = 0; s < NSTG - 1; ++s)
@@ -311,31 +296,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_pp_kernel(PPArgs P, un
     }
 
     float *__restrict__ C = P.C;
-    if (m0 + BM <= P.M && n0 + BN <= P.N && (long long)BM * P.ldc < (1LL << 30)) {
-        float *__restrict__ cw = C + (size_t)(m0 + wm * TM * 32) * P.ldc + (n0 + wn * TN * 32);
-        const unsigned ldc = (unsigned)P.ldc;
-        const unsigned lane_off = 4u * lj * ldc + li;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const unsigned o = lane_off + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldc;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) cw[o + j * 32] = acc[i][j][r];
-            }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wn * TN + j) * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lj;
-                if (m < P.M && n < P.N) C[m * P.ldc + n] = acc[i][j][r];
-            }
-        }
+    EPN_NT_STORE_TILE(float, C)
 }
 
 template <int WGM, int WGN, int TM, int TN, int NSTG, int KS>

@@ -15,7 +15,9 @@
 //                                        [3][N][K] (workspace), which the kernel stages like bf16 operands.
 //
 // Staging, swizzles and the epilogue follow gemm_nt_kernel (gemm.hip); the K step is 32 values (128-byte fp32 rows of
-// A, three 64-byte bf16 rows per weight row).
+// A, three 64-byte bf16 rows per weight row).  Host side: the instances are named once in EPN_X3_INSTANCES, x3_choose holds
+// the selection rule, planes_bytes / f2_prob_bytes the workspace layout (queries and carving); the tile planner and the
+// marshalling of the entry points' problems are shared with gemm.hip (gemm.h: nt_plan_tiles, nt_marshal / nt_for_chunks).
 #include "conv_internal.h"
 #include "gemm.h"
 
@@ -35,14 +37,8 @@ __global__ void split_planes_kernel(const float *__restrict__ W, long long ldw, 
     const int k2 = K >> 1;
     if (i >= (long long)N * k2) return;
     const int n = (int)(i / k2), k = 2 * (int)(i % k2);
-    const float x0 = W[n * ldw + k], x1 = W[n * ldw + k + 1];
-    const unsigned hp = pack_rne(x0, x1);
-    const float r0 = x0 - lo_f(hp), r1 = x1 - hi_f(hp);
-    const unsigned mp = pack_rne(r0, r1);
     const size_t plane = (size_t)N * k2;
-    planes[i] = hp;
-    planes[plane + i] = mp;
-    planes[2 * plane + i] = pack_rne(r0 - lo_f(mp), r1 - hi_f(mp));
+    EPN_SPLIT3_PAIR_STORE(W[n * ldw + k], W[n * ldw + k + 1], planes, plane, i);
 }
 
 // the weights of all problems of a grouped launch (the five blocks of a spectral IntraSO3Conv) in ONE launch: blockIdx.y =
@@ -61,13 +57,7 @@ __global__ void split_planes_batch_kernel(SplitBatch S) {
     const size_t plane = (size_t)N * k2;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (long long)N * k2; i += (long long)gridDim.x * blockDim.x) {
         const int n = (int)(i / k2), k = 2 * (int)(i % k2);
-        const float x0 = W[n * S.ldw[q] + k], x1 = W[n * S.ldw[q] + k + 1];
-        const unsigned hp = pack_rne(x0, x1);
-        const float r0 = x0 - lo_f(hp), r1 = x1 - hi_f(hp);
-        const unsigned mp = pack_rne(r0, r1);
-        planes[i] = hp;
-        planes[plane + i] = mp;
-        planes[2 * plane + i] = pack_rne(r0 - lo_f(mp), r1 - hi_f(mp));
+        EPN_SPLIT3_PAIR_STORE(W[n * S.ldw[q] + k], W[n * S.ldw[q] + k + 1], planes, plane, i);
     }
 }
 
@@ -100,11 +90,7 @@ __global__ __launch_bounds__(256) void split_rows2_batch_kernel(Split2Batch S) {
             m = (a > m && a < 0x7f800000u) ? a : m;
             m = (b > m && b < 0x7f800000u) ? b : m;
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const unsigned v = (unsigned)__shfl_xor((int)m, o, 64);
-            m = v > m ? v : m;
-        }
+        EPN_WAVE_UMAX(m)
         const float amax = __builtin_bit_cast(float, m);
         const float sc = f2_scale_of(amax);
         if (lane == 0) S.rowmax[q][n] = amax;
@@ -124,21 +110,14 @@ __global__ __launch_bounds__(256) void split_rows2_batch_kernel(Split2Batch S) {
 // (launch_absmax).  A streaming read: four independent 16-byte loads per thread and iteration.
 __device__ __forceinline__ unsigned absmax4(unsigned m, const u32x4 v) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const unsigned a = v[k] & 0x7fffffffu;
-        m = (a > m && a < 0x7f800000u) ? a : m;
-    }
+    for (int k = 0; k < 4; ++k) m = absmax_finite(m, v[k]);
     return m;
 }
 // one atomic per WORKGROUP, and only when it would raise the value: 8192 waves hammering one address made the pass over a 126 MB
 // operand take 105 us (1.2 TB/s) -- the maximum is monotonic, so a stale read only costs an atomic that changes nothing
 __device__ __forceinline__ void absmax_finish(unsigned m, unsigned *out) {      // blockDim.x == 256
     __shared__ unsigned red[4];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned v = (unsigned)__shfl_xor((int)m, o, 64);
-        m = v > m ? v : m;
-    }
+    EPN_WAVE_UMAX(m)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -176,8 +155,7 @@ __global__ void absmax_tail_kernel(const float *__restrict__ src, long long ld, 
     unsigned m = 0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const long long r = i / w, c = c0 + (i - r * w);
-        const unsigned a = __builtin_bit_cast(unsigned, src[r * ld + c]) & 0x7fffffffu;
-        m = (a > m && a < 0x7f800000u) ? a : m;
+        m = absmax_finite(m, __builtin_bit_cast(unsigned, src[r * ld + c]));
     }
     if (m) atomicMax(out, m);
 }
@@ -199,15 +177,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_x3_kernel(GemmNtBatch 
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int pi = 0;
-#pragma unroll
-    for (int i = 1; i < GEMM_MAX_PROB; ++i)
-        if (i < B.nprob && blockIdx.x >= B.p[i].tile0) pi = i;
-    const GemmNtProb &P = B.p[pi];
-    if (blockIdx.x - P.tile0 >= P.ntile) return;
-    const unsigned t = epn_xcd_tile(blockIdx.x - P.tile0, P.ntile);
-    const long long m0 = (long long)(t / P.tiles_n) * BM;
-    const int n0 = (int)(t % P.tiles_n) * BN;
+    EPN_NT_DECODE(B)
     const int nk = P.K / 32;
 
     const char *src[GPW];
@@ -235,9 +205,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_x3_kernel(GemmNtBatch 
     auto stage_one = [&](int buf, int i) {
         const int g = wave + i * NW;
         if (NG % NW == 0 || g < NG) {
-#ifdef EPN_X3_NTA
-            if (g < NGA) glds16_nt(src[i], smem + buf * STAGE + g * 1024); else
-#endif
             glds16(src[i], smem + buf * STAGE + g * 1024);
             src[i] += adv[i];
         }
@@ -264,12 +231,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_x3_kernel(GemmNtBatch 
     for (int i = 0; i < TN; ++i) boff[i] = A_BYTES + ((wn * TN + i) * 32 + li) * 64;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    EPN_NT_ZERO_ACC(acc)
 
     stage(0);
     if constexpr (NSTG == 3) {
@@ -380,62 +342,83 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_x3_kernel(GemmNtBatch 
     // idle stage buffers and stored as 16-byte pieces of whole rows, 8x fewer store instructions: 2-7 % SLOWER on every
     // output-heavy shape (245760 x 6144 x 256: 2.88 -> 2.94 ms, 983040 x 1536 x 64: 1.25 -> 1.35).  The store tail of these tiles
     // is not bound by store issue; the direct form's 128-byte row segments are already whole cache lines.)
-    if (m0 + BM <= P.M && n0 + BN <= P.N && (long long)BM * P.ldc < (1LL << 30)) {
-        float *__restrict__ cw = C + (size_t)(m0 + wm * TM * 32) * P.ldc + (n0 + wn * TN * 32);
-        const unsigned ldc = (unsigned)P.ldc;
-        const unsigned lane_off = 4u * lj * ldc + li;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const unsigned o = lane_off + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldc;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-#ifdef EPN_X3_NTC
-                    __builtin_nontemporal_store(acc[i][j][r], cw + o + j * 32);
-#else
-                    cw[o + j * 32] = acc[i][j][r];
-#endif
-                }
-            }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wn * TN + j) * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lj;
-                if (m < P.M && n < P.N) C[m * P.ldc + n] = acc[i][j][r];
-            }
-        }
+    EPN_NT_STORE_TILE(float, C)
 }
 
 template <int WGM, int WGN, int TM, int TN, int NSTG, int NPL = 3>
 int launch_x3_cfg(GemmNtBatch &B, hipStream_t st) {
-    constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
-    for (int i = 1; i < B.nprob; ++i)           // longest contraction first (see launch_nt_cfg)
-        for (int k = i; k > 0 && B.p[k].K > B.p[k - 1].K; --k) {
-            const GemmNtProb tmp = B.p[k]; B.p[k] = B.p[k - 1]; B.p[k - 1] = tmp;
-        }
-    unsigned total = 0;
-    for (int i = 0; i < B.nprob; ++i) {
-        GemmNtProb &p = B.p[i];
-        p.tiles_n = (p.N + BN - 1) / BN;
-        p.tile0 = total;
-        p.ntile = (unsigned)((p.M + BM - 1) / BM) * p.tiles_n;
-        total += i + 1 < B.nprob ? (p.ntile + 7u) & ~7u : p.ntile;
-    }
-    B.ntiles = total;
+    const unsigned total = nt_plan_tiles(B, WGM * TM * 32, WGN * TN * 32);
     if (total == 0) return 0;
     EPN_LAUNCH((gemm_nt_x3_kernel<WGM, WGN, TM, TN, NSTG, NPL>), dim3(total), dim3(64 * WGM * WGN), 0, st, B);
     EPN_CHECK_LAUNCH();
     return 0;
 }
 
-inline size_t planes_bytes(const GemmNtProb &p) { return ((size_t)6 * p.N * p.K + 255) & ~(size_t)255; }
+// ------------------------------------------------------------------------------------------------ the kernel instances
+// Every gemm_nt_x3_kernel<..., NPL> instance is named ONCE, here, for NPL = 3 and 2: X(code, WGM, WGN, TM, TN, NSTG); block tile
+// (WGM*TM*32) x (WGN*TN*32); code = policy code of the tuning override (tools/x3_probe.py).  x3_choose() names a tuple;
+// launch_x3_instance() looks it up and fails with EPN_EINVAL when there is none.  "override only": instantiated, but no rule
+// of x3_choose reaches it (kept: the code object stays what it was).
+#define EPN_X3_INSTANCES(X)                                                                                          \
+    X(0x21, 4, 2, 2, 2, 2) /* 256 x 128, 8 waves */                                                                  \
+    X(0x22, 4, 2, 2, 4, 2) /* 256 x 256, 8 waves (all of the LDS in the bf16 form) */                                \
+    X(0x23, 2, 2, 2, 2, 2) /* 128 x 128, 4 waves */                                                                  \
+    X(0x24, 2, 2, 2, 2, 3) /* override only */                                                                       \
+    X(0x25, 4, 1, 2, 2, 3) /* 256 x 64, 4 waves (NPL = 2: override only) */                                          \
+    X(0x26, 4, 1, 2, 2, 2) /* (NPL = 3: override only) */                                                            \
+    X(0x27, 2, 2, 4, 2, 2) /* 256 x 128, 4 waves (128 x 64 per wave): override only */                               \
+    X(0x28, 2, 4, 2, 2, 2) /* 128 x 256, 8 waves: override only */                                                   \
+    X(0x29, 2, 2, 2, 4, 2) /* 128 x 256, 4 waves: override only */                                                   \
+    X(0x2a, 8, 1, 2, 1, 2) /* 512 x 32 */
+// NPL == 2 only (three stages of the three-piece form do not fit the LDS)
+#define EPN_X3_F2_INSTANCES(X) X(0x2b, 4, 2, 2, 2, 3) /* 256 x 128, three stages (144 KB): override only */
+
+struct X3Tile { int wgm, wgn, tm, tn, nstg; };
+
+// the selection rule; npl = 3 / 2 pieces, policy: kernel_policy()
+inline X3Tile x3_choose(int npl, int nprob, int maxn, int minn, int policy) {
+    if ((policy & ~0xff) == 0x100) {            // tuning override (tools/x3_probe.py); a code without entry: the rules
+#define EPN_X3_CODE(CODE, ...) if ((policy & 0xff) == CODE) return {__VA_ARGS__};
+        EPN_X3_INSTANCES(EPN_X3_CODE)
+        if (npl == 2) { EPN_X3_F2_INSTANCES(EPN_X3_CODE) }
+#undef EPN_X3_CODE
+    }
+    // 256 x 64 tiles: three stages (120-132 KB: one workgroup per CU) in the three-piece form; the two-piece form's stage is
+    // 40 KB, and TWO stages leave room for two workgroups per CU -- what the short contractions of these narrow problems want
+    // (c = 64 spectral groups 0.214 -> 0.171 ms, 983040 x 64 x 64 0.120 -> 0.105, 491520 x 64 x 128 0.099 -> 0.089; the long
+    // K = 1536 forward GEMM of the cout = 64 layer is unchanged at 1.12 ms: tools/spectral_nt_probe.py)
+    const int nstg64 = npl == 2 ? 2 : 3;
+    if (nprob > 1) {                            // grouped spectral blocks: ragged widths, narrow tiles (see nt_choose, gemm.hip)
+        if (maxn <= 320 && minn <= 64) return {4, 1, 2, 2, nstg64};
+        if (minn >= 256) return {4, 2, 2, 4, 2};   // c = 256 blocks: 0.76 -> 0.68 ms (A is re-read per tile column)
+        return {2, 2, 2, 2, 2};
+    }
+    if (maxn <= 32) return {8, 1, 2, 1, 2};
+    if (maxn <= 64) return {4, 1, 2, 2, nstg64};
+    // cout <= 128 in the two-piece form: 128 x 128 tiles of four waves (64 KB of stages: two workgroups per CU) edge out the
+    // 256 x 128 tile (491520 x 128 x 1536: 0.857 -> 0.819 ms cold, x 3072: 1.617 -> 1.573, x 128: 0.125 -> 0.116; tools/nt_tile_probe.py)
+    if (npl == 2 && maxn <= 128) return {2, 2, 2, 2, 2};
+    if (maxn <= 128 || maxn % 256 > 128 || (maxn % 256 && maxn < 512)) return {4, 2, 2, 2, 2};
+    return {4, 2, 2, 4, 2};
+}
+
+// launches the instance `c` names; EPN_EINVAL when the tables above have none for this NPL
+template <int NPL>
+int launch_x3_instance(const X3Tile &c, GemmNtBatch &B, hipStream_t st) {
+#define EPN_X3_TRY(CODE, WGM, WGN, TM, TN, NSTG)                                                                     \
+    if (c.wgm == WGM && c.wgn == WGN && c.tm == TM && c.tn == TN && c.nstg == NSTG)                                  \
+        return launch_x3_cfg<WGM, WGN, TM, TN, NSTG, NPL>(B, st);
+    EPN_X3_INSTANCES(EPN_X3_TRY)
+    if constexpr (NPL == 2) { EPN_X3_F2_INSTANCES(EPN_X3_TRY) }
+#undef EPN_X3_TRY
+    return EPN_EINVAL;
+}
+
+// workspace of one problem, 256-byte pieces: the three-piece form's bf16 planes [3][N][K] (npl = 2: the fp16 planes [2][N][K]);
+// the two-piece form's planes + row maxima [N].  The queries and the carving of launch_gemm_nt_x3 both go by these two.
+inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+inline size_t planes_bytes(long long N, long long K, int npl = 3) { return al256((size_t)2 * npl * N * K); }
+inline size_t f2_prob_bytes(long long N, long long K) { return planes_bytes(N, K, 2) + al256((size_t)4 * N); }
 
 }  // namespace
 
@@ -452,14 +435,11 @@ bool gemm_nt_x3_ok(const GemmNtBatch &B) {
 
 size_t gemm_nt_x3_workspace(const GemmNtBatch &B) {
     size_t n = 0;
-    for (int i = 0; i < B.nprob; ++i) n += planes_bytes(B.p[i]);
+    for (int i = 0; i < B.nprob; ++i) n += planes_bytes(B.p[i].N, B.p[i].K);
     return n;
 }
 
 // two-piece form: a_amax slot per problem (256 B), then per problem the fp16 planes [2][N][K] and the row maxima [N]
-static size_t f2_prob_bytes(long long N, long long K) {
-    return (((size_t)4 * N * K + 255) & ~(size_t)255) + (((size_t)4 * N + 255) & ~(size_t)255);
-}
 size_t gemm_nt_f2_workspace(const GemmNtBatch &B) {
     size_t n = 256;
     for (int i = 0; i < B.nprob; ++i) n += f2_prob_bytes(B.p[i].N, B.p[i].K);
@@ -535,44 +515,6 @@ int launch_absmax(const float *src, long long ld, long long rows, long long cols
     return 0;
 }
 
-template <int NPL>
-static int x3_dispatch(GemmNtBatch &B, int maxn, int minn, hipStream_t st) {
-    const int pol = kernel_policy();
-    if ((pol & ~0xff) == 0x100) {               // tuning override (tools/x3_probe.py)
-        switch (pol & 0xff) {
-            case 0x21: return launch_x3_cfg<4, 2, 2, 2, 2, NPL>(B, st);     // 256 x 128, 8 waves
-            case 0x22: return launch_x3_cfg<4, 2, 2, 4, 2, NPL>(B, st);     // 256 x 256, 8 waves (all of the LDS in the bf16 form)
-            case 0x23: return launch_x3_cfg<2, 2, 2, 2, 2, NPL>(B, st);     // 128 x 128, 4 waves
-            case 0x24: return launch_x3_cfg<2, 2, 2, 2, 3, NPL>(B, st);
-            case 0x25: return launch_x3_cfg<4, 1, 2, 2, 3, NPL>(B, st);     // 256 x 64, 4 waves
-            case 0x26: return launch_x3_cfg<4, 1, 2, 2, 2, NPL>(B, st);
-            case 0x27: return launch_x3_cfg<2, 2, 4, 2, 2, NPL>(B, st);     // 256 x 128, 4 waves (128 x 64 per wave)
-            case 0x28: return launch_x3_cfg<2, 4, 2, 2, 2, NPL>(B, st);     // 128 x 256, 8 waves
-            case 0x29: return launch_x3_cfg<2, 2, 2, 4, 2, NPL>(B, st);     // 128 x 256, 4 waves
-            case 0x2a: return launch_x3_cfg<8, 1, 2, 1, 2, NPL>(B, st);     // 512 x 32
-            case 0x2b: if constexpr (NPL == 2) return launch_x3_cfg<4, 2, 2, 2, 3, NPL>(B, st); else break;   // 256 x 128, three stages (144 KB)
-            default: break;
-        }
-    }
-    // 256 x 64 tiles: three stages (120-132 KB: one workgroup per CU) in the three-piece form; the two-piece form's stage is
-    // 40 KB, and TWO stages leave room for two workgroups per CU -- what the short contractions of these narrow problems want
-    // (c = 64 spectral groups 0.214 -> 0.171 ms, 983040 x 64 x 64 0.120 -> 0.105, 491520 x 64 x 128 0.099 -> 0.089; the long
-    // K = 1536 forward GEMM of the cout = 64 layer is unchanged at 1.12 ms: tools/spectral_nt_probe.py)
-    constexpr int NSTG64 = NPL == 2 ? 2 : 3;
-    if (B.nprob > 1) {                          // grouped spectral blocks: ragged widths, narrow tiles (see launch_nt_typed)
-        if (maxn <= 320 && minn <= 64) return launch_x3_cfg<4, 1, 2, 2, NSTG64, NPL>(B, st);
-        if (minn >= 256) return launch_x3_cfg<4, 2, 2, 4, 2, NPL>(B, st);   // c = 256 blocks: 0.76 -> 0.68 ms (A is re-read per tile column)
-        return launch_x3_cfg<2, 2, 2, 2, 2, NPL>(B, st);
-    }
-    if (maxn <= 32) return launch_x3_cfg<8, 1, 2, 1, 2, NPL>(B, st);
-    if (maxn <= 64) return launch_x3_cfg<4, 1, 2, 2, NSTG64, NPL>(B, st);
-    // cout <= 128 in the two-piece form: 128 x 128 tiles of four waves (64 KB of stages: two workgroups per CU) edge out the
-    // 256 x 128 tile (491520 x 128 x 1536: 0.857 -> 0.819 ms cold, x 3072: 1.617 -> 1.573, x 128: 0.125 -> 0.116; tools/nt_tile_probe.py)
-    if (NPL == 2 && maxn <= 128) return launch_x3_cfg<2, 2, 2, 2, 2, NPL>(B, st);
-    if (maxn <= 128 || maxn % 256 > 128 || (maxn % 256 && maxn < 512)) return launch_x3_cfg<4, 2, 2, 2, 2, NPL>(B, st);
-    return launch_x3_cfg<4, 2, 2, 4, 2, NPL>(B, st);
-}
-
 // npl = 3: lossless three-piece bf16 form (planes of the weights in `ws`); npl = 2: two-piece fp16 form -- `ws` starts with
 // the amax slots ([2 i] = max|A_i| when the caller gave none in p.a_amax, [2 i + 1] = max|Bt_i|), then the fp16 planes
 int launch_gemm_nt_x3(GemmNtBatch &B, void *ws, size_t ws_bytes, hipStream_t st, int npl) {
@@ -605,17 +547,16 @@ int launch_gemm_nt_x3(GemmNtBatch &B, void *ws, size_t ws_bytes, hipStream_t st,
             S.W[i] = static_cast<const float *>(p.Bt); S.planes[i] = reinterpret_cast<unsigned *>(w); S.ldw[i] = p.ldb;
             S.N[i] = p.N; S.K[i] = p.K;
             p.Bp = w;
-            w += ((size_t)4 * p.N * p.K + 255) & ~(size_t)255;
-            S.rowmax[i] = reinterpret_cast<float *>(w);
+            S.rowmax[i] = reinterpret_cast<float *>(w + planes_bytes(p.N, p.K, 2));
             p.b_amax = S.rowmax[i];
-            w += ((size_t)4 * p.N + 255) & ~(size_t)255;
+            w += f2_prob_bytes(p.N, p.K);
             rows_max = p.N > rows_max ? p.N : rows_max;
         }
         // a wave per weight row
         const unsigned gr = (unsigned)((rows_max + 3) / 4 < 2048 ? (rows_max + 3) / 4 : 2048);
         EPN_LAUNCH_AUX(split_rows2_batch_kernel, dim3(gr, B.nprob), dim3(256), 0, st, S);
         EPN_CHECK_LAUNCH();
-        return x3_dispatch<2>(B, maxn, minn, st);
+        return launch_x3_instance<2>(x3_choose(2, B.nprob, maxn, minn, kernel_policy()), B, st);
     }
     SplitBatch S;
     for (int i = 0; i < B.nprob; ++i) {
@@ -623,7 +564,7 @@ int launch_gemm_nt_x3(GemmNtBatch &B, void *ws, size_t ws_bytes, hipStream_t st,
         S.W[i] = static_cast<const float *>(p.Bt); S.planes[i] = reinterpret_cast<unsigned *>(w); S.ldw[i] = p.ldb;
         S.N[i] = p.N; S.K[i] = p.K;
         p.Bp = w;
-        w += planes_bytes(p);
+        w += planes_bytes(p.N, p.K);
     }
     if (B.nprob == 1) {
         EPN_LAUNCH_AUX(split_planes_kernel, dim3((unsigned)((maxpairs + 255) / 256)), dim3(256), 0, st, S.W[0], S.ldw[0], S.N[0],
@@ -632,7 +573,7 @@ int launch_gemm_nt_x3(GemmNtBatch &B, void *ws, size_t ws_bytes, hipStream_t st,
         EPN_LAUNCH_AUX(split_planes_batch_kernel, dim3(gx, B.nprob), dim3(256), 0, st, S);
     }
     EPN_CHECK_LAUNCH();
-    return x3_dispatch<3>(B, maxn, minn, st);
+    return launch_x3_instance<3>(x3_choose(3, B.nprob, maxn, minn, kernel_policy()), B, st);
 }
 
 }  // namespace epn
@@ -642,33 +583,21 @@ using namespace epn;
 extern "C" size_t epn_gemm_nt_split_workspace_bytes(int nprob, const epn_gemm_nt_problem *probs) {
     if (!probs || nprob < 1) return 0;
     size_t n = 0;
-    for (int i = 0; i < nprob; ++i) n += (((size_t)6 * probs[i].N * probs[i].K + 255) & ~(size_t)255);
+    for (int i = 0; i < nprob; ++i) n += planes_bytes(probs[i].N, probs[i].K);
     return n;
 }
 
 extern "C" int epn_gemm_nt_split_f32(int nprob, const epn_gemm_nt_problem *probs, void *workspace, size_t workspace_bytes,
                                      epn_stream_t stream) {
-    if (!probs) return EPN_ENULL;
-    if (nprob < 1) return EPN_EINVAL;
-    hipStream_t st = epn_stream(stream);
     char *w = static_cast<char *>(workspace);
     size_t left = workspace ? workspace_bytes : 0;
-    for (int i0 = 0; i0 < nprob; i0 += GEMM_MAX_PROB) {
-        GemmNtBatch B;
-        B.nprob = nprob - i0 < GEMM_MAX_PROB ? nprob - i0 : GEMM_MAX_PROB;
-        for (int i = 0; i < B.nprob; ++i) {
-            const epn_gemm_nt_problem &q = probs[i0 + i];
-            GemmNtProb &p = B.p[i];
-            p.A = q.A; p.Bt = q.Bt; p.C = q.C; p.M = q.M; p.N = q.N; p.K = q.K; p.lda = q.lda; p.ldb = q.ldb; p.ldc = q.ldc;
-            p.tiles_n = 0; p.tile0 = 0; p.ntile = 0; p.Bp = nullptr; p.stats = q.col_stats; p.c_amax = reinterpret_cast<unsigned *>(q.c_amax);
-            p.a_amax = p.b_amax = nullptr;
-        }
+    return nt_for_chunks(nprob, probs, nullptr, [&](GemmNtBatch &B) {
         const size_t need = gemm_nt_x3_workspace(B);
-        int rc = launch_gemm_nt_x3(B, need <= left ? w : nullptr, need <= left ? need : 0, st);
-        if (rc) return rc;
-        if (need <= left) { w += need; left -= need; }
-    }
-    return 0;
+        const bool have = need <= left;         // a short workspace: this launch runs on the fp32 kernels, silently
+        const int rc = launch_gemm_nt_x3(B, have ? w : nullptr, have ? need : 0, epn_stream(stream));
+        if (have) { w += need; left -= need; }
+        return rc;
+    });
 }
 
 extern "C" int epn_absmax_f32(const float *src, long long ld, long long rows, long long cols, float *out, epn_stream_t stream) {
@@ -697,26 +626,13 @@ extern "C" size_t epn_gemm_nt_f16x2_workspace_bytes(int nprob, const epn_gemm_nt
 
 extern "C" int epn_gemm_nt_f16x2_f32(int nprob, const epn_gemm_nt_problem *probs, const float *const *a_amax, void *workspace,
                                      size_t workspace_bytes, epn_stream_t stream) {
-    if (!probs) return EPN_ENULL;
-    if (nprob < 1) return EPN_EINVAL;
-    hipStream_t st = epn_stream(stream);
     char *w = static_cast<char *>(workspace);
     size_t left = workspace ? workspace_bytes : 0;
-    for (int i0 = 0; i0 < nprob; i0 += GEMM_MAX_PROB) {
-        GemmNtBatch B;
-        B.nprob = nprob - i0 < GEMM_MAX_PROB ? nprob - i0 : GEMM_MAX_PROB;
-        for (int i = 0; i < B.nprob; ++i) {
-            const epn_gemm_nt_problem &q = probs[i0 + i];
-            GemmNtProb &p = B.p[i];
-            p.A = q.A; p.Bt = q.Bt; p.C = q.C; p.M = q.M; p.N = q.N; p.K = q.K; p.lda = q.lda; p.ldb = q.ldb; p.ldc = q.ldc;
-            p.tiles_n = 0; p.tile0 = 0; p.ntile = 0; p.Bp = nullptr; p.stats = q.col_stats; p.c_amax = reinterpret_cast<unsigned *>(q.c_amax);
-            p.a_amax = a_amax ? a_amax[i0 + i] : nullptr; p.b_amax = nullptr;
-        }
+    return nt_for_chunks(nprob, probs, a_amax, [&](GemmNtBatch &B) {
         const size_t need = gemm_nt_f2_workspace(B);
-        if (need > left) return EPN_EWORKSPACE;
-        int rc = launch_gemm_nt_x3(B, w, need, st, 2);
-        if (rc) return rc;
+        if (need > left) return (int)EPN_EWORKSPACE;
+        const int rc = launch_gemm_nt_x3(B, w, need, epn_stream(stream), 2);
         w += need; left -= need;
-    }
-    return 0;
+        return rc;
+    });
 }

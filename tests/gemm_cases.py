@@ -1,5 +1,5 @@
 """Case tables of tests/test_gpu_gemm_exact.py, the exactness condition they stand on, and a Python restatement of the GEMM
-dispatch tables (csrc/gemm.hip launch_nt_typed, csrc/gemm_x3.hip gemm_nt_x3_ok / x3_dispatch, csrc/gemm_tn.hip gemm_tn_tile /
+dispatch tables (csrc/gemm.hip launch_nt_typed / nt_choose, csrc/gemm_x3.hip gemm_nt_x3_ok / x3_choose, csrc/gemm_tn.hip gemm_tn_tile /
 gemm_tn_splits / tn_fast_ok / tn_plan) that says which kernel instance a case must reach.  tests/test_gemm_spec.py checks on the
 CPU that every case is in the exact regime, that the restated split counts agree with the library's workspace queries, and that
 the cases reach every instance listed in REACHABLE; the GPU file asserts per call that the library ran the predicted instance.
