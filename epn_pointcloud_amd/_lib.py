@@ -62,6 +62,7 @@ EXPORTS = [
     "epn_rotation_labels_f32", "epn_so3_mean_f32", "epn_rotation_decode_f32",
     "epn_ransac_register_workspace_bytes", "epn_ransac_register_f64",
     "epn_triplet_batch_hard_f32", "epn_triplet_batch_hard_bwd_f32", "epn_anchor_interp_f32", "epn_anchor_interp_bwd_f32",
+    "epn_rotation_loss_f32", "epn_rotation_loss_bwd_f32",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -345,6 +346,10 @@ def get_lib():
     lib.epn_triplet_batch_hard_bwd_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cd, _vp, _vp, _vp]
     lib.epn_anchor_interp_f32.argtypes = [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _cd, _vp, _vp, _vp, _vp]
     lib.epn_anchor_interp_bwd_f32.argtypes = [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
+    # training loss of the rotation network: (wts, y, label, R_target, b, A, nr, w, row_ce, row_l2, preds, row_flags, sel_R,
+    # scalars), (upstream, wts, y, label, R_target, row_flags, b, A, nr, w, dwts, dy)
+    lib.epn_rotation_loss_f32.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.epn_rotation_loss_bwd_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cd, _vp, _vp, _vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

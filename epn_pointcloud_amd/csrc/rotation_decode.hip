@@ -25,7 +25,7 @@
 namespace {
 
 using epn_rot::acos_safe;
-using epn_rot::quat_matrix;
+using epn_rot::rotation_map;
 using epn_rot::so3_project;
 
 constexpr int RW = 64;                   // threads per workgroup = one wave = the most anchors
@@ -39,20 +39,6 @@ __device__ __forceinline__ double wave_sum(double x) {
 __device__ __forceinline__ void load9(const float *__restrict__ p, double m[9]) {
 #pragma unroll
     for (int e = 0; e < 9; ++e) m[e] = (double)p[e];
-}
-
-// v / max(|v|, 1e-8): normalize_vector of rotation.py:381-390
-__device__ __forceinline__ void normalize(double *v, int n) {
-    double s = 0.0;
-    for (int e = 0; e < n; ++e) s += v[e] * v[e];
-    const double mag = fmax(sqrt(s), 1e-8);
-    for (int e = 0; e < n; ++e) v[e] /= mag;
-}
-
-__device__ __forceinline__ void cross(const double u[3], const double v[3], double o[3]) {
-    o[0] = u[1] * v[2] - u[2] * v[1];
-    o[1] = u[2] * v[0] - u[0] * v[2];
-    o[2] = u[0] * v[1] - u[1] * v[0];
 }
 
 __global__ __launch_bounds__(RW) void rotation_labels_kernel(const float *__restrict__ anchors, const float *__restrict__ T, int A,
@@ -139,23 +125,8 @@ __global__ __launch_bounds__(RW) void rotation_decode_kernel(const float *__rest
         double v[NR];
 #pragma unroll
         for (int e = 0; e < NR; ++e) v[e] = (double)yp[e * AA];
-        double Ra[9];
-        if (NR == 4) {
-            normalize(v, 4);
-            quat_matrix(v, Ra);
-        } else {
-            double x[3] = {v[0], v[1], v[2]}, yr[3] = {v[NR - 3], v[NR - 2], v[NR - 1]}, z[3], yy[3];
-            normalize(x, 3);
-            cross(x, yr, z);
-            normalize(z, 3);
-            cross(z, x, yy);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                Ra[3 * i] = x[i];
-                Ra[3 * i + 1] = yy[i];
-                Ra[3 * i + 2] = z[i];
-            }
-        }
+        double Ra[9], norms[2];
+        rotation_map<NR>(v, Ra, norms);
         double Aa[9], Ap[9], M[9];
         load9(anchors + 9 * a, Aa);
         load9(anchors + 9 * p, Ap);

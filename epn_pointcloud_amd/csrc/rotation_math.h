@@ -1,5 +1,6 @@
-// The arithmetic of csrc/rotation_decode.hip that needs no device: the quaternion's rotation matrix, the projection of a 3 x 3
-// matrix onto SO(3) with its conditioning margin, and acos_safe.  Plain C++ on doubles, compiled into the kernels by hipcc and
+// The arithmetic of csrc/rotation_decode.hip and csrc/rotation_loss.hip that needs no device: the quaternion's rotation matrix,
+// the two rotation maps of the head's output, the projection of a 3 x 3 matrix onto SO(3) with its conditioning margin, and
+// acos_safe.  Plain C++ on doubles, compiled into the kernels by hipcc and
 // into a host program by any C++ compiler (tools/so3_project_host.cpp, which tests/test_rotation_host.py builds with the
 // address and undefined-behaviour sanitizers and compares with numpy's SVD at every conditioning).
 #pragma once
@@ -22,6 +23,46 @@ EPN_ROT_FN void quat_matrix(const double q[4], double R[9]) {
     R[0] = 1.0 - 2.0 * yy - 2.0 * zz; R[1] = 2.0 * xy - 2.0 * zw;       R[2] = 2.0 * xz + 2.0 * yw;
     R[3] = 2.0 * xy + 2.0 * zw;       R[4] = 1.0 - 2.0 * xx - 2.0 * zz; R[5] = 2.0 * yz - 2.0 * xw;
     R[6] = 2.0 * xz - 2.0 * yw;       R[7] = 2.0 * yz + 2.0 * xw;       R[8] = 1.0 - 2.0 * xx - 2.0 * yy;
+}
+
+// v / max(|v|, 1e-8) in place: normalize_vector of rotation.py:381-390.  -> |v| as it was, before the clamp
+EPN_ROT_FN double normalize(double *v, int n) {
+    double s = 0.0;
+    for (int e = 0; e < n; ++e) s += v[e] * v[e];
+    const double norm = sqrt(s), mag = fmax(norm, 1e-8);
+    for (int e = 0; e < n; ++e) v[e] /= mag;
+    return norm;
+}
+
+EPN_ROT_FN void cross(const double u[3], const double v[3], double o[3]) {
+    o[0] = u[1] * v[2] - u[2] * v[1];
+    o[1] = u[2] * v[0] - u[0] * v[2];
+    o[2] = u[0] * v[1] - u[1] * v[0];
+}
+
+// The two rotation maps of the head's y entries (rotation.py:379-417 and :443-478), shared by the decode and the loss.
+// NR = 4: v <- q / max(|q|, 1e-8), R = quat_matrix(v), norms[0] = norms[1] = |q|.  NR = 6: x = n(v[0:3]), z = n(x cross v[3:6]),
+// y = z cross x, n(u) = u / max(|u|, 1e-8); R's columns are (x, y, z), norms = (|v[0:3]|, |x cross v[3:6]|) and v[0:3] <- x
+// (v[3:6] stays as it was): what a backward through the map needs besides R.
+template <int NR>
+EPN_ROT_FN void rotation_map(double v[NR], double R[9], double norms[2]) {
+    if (NR == 4) {
+        norms[0] = norms[1] = normalize(v, 4);
+        quat_matrix(v, R);
+    } else {
+        double x[3] = {v[0], v[1], v[2]}, yr[3] = {v[NR - 3], v[NR - 2], v[NR - 1]}, z[3], yy[3];
+        norms[0] = normalize(x, 3);
+        cross(x, yr, z);
+        norms[1] = normalize(z, 3);
+        cross(z, x, yy);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            R[3 * i] = x[i];
+            R[3 * i + 1] = yy[i];
+            R[3 * i + 2] = z[i];
+            v[i] = x[i];
+        }
+    }
 }
 
 // The rotation R maximising tr(R^T Ce) and margin = (s2 + det(U V^T) s3) / s1 of Ce's singular values.

@@ -7,6 +7,11 @@ DESIGN.md 3.1d; kernels: csrc/triplet_loss.hip.  Forward two launches (one for t
 synchronises with the host and nothing indexes with a boolean mask, so a step that ends in this loss can be captured into a
 HIP graph -- the reference's dist_mat[is_neg] (loss.py:234) cannot.
 
+And the rotation network's: rotation_loss, the alignment branch of the reference's MultiTaskDetectionLoss (loss.py:140-181) --
+anchor cross-entropy plus the L2 distance of the regressed relative rotations -- the loss SPConvNets/trainer_modelnetRotation.py
+trains with.  Specification: epn_rotation_loss_f32 and its backward; kernels: csrc/rotation_loss.hip.  Forward
+two launches, backward one, under the same rules.
+
 Shapes and dtypes are checked on the host before the device is touched: type, shape, dtype, then device."""
 import collections
 
@@ -112,6 +117,117 @@ def batch_hard_triplet(src, tgt, mode="hard", margin=1.0):
     its nearest other tgt row.  loss.backward() reaches src and tgt through one launch; accuracy, pos and neg are for logging
     and carry no gradient."""
     return batch_hard_rows(src, tgt, mode, margin)[0]
+
+
+RotationLossResult = collections.namedtuple("RotationLossResult", "loss cls_loss reg r_acc preds row_ce row_l2 row_flags")
+RotationLossResult.__doc__ = """rotation_loss's result: loss (f32 scalar, cls_loss + reg; the only differentiable field), cls_loss
+(the mean cross-entropy over the b * A rows), reg (w times the mean squared difference of the selected rotations to R_target),
+r_acc (share of rows whose most confident target anchor is the label) -- the first four values MultiTaskDetectionLoss.forward
+returns -- and per row [b,A]: preds int32 (the most confident target anchor, the lowest on a tie), row_ce and row_l2 f32,
+row_flags int32 (bit 0: the label lies outside 0..A-1 and the row counts as zero; bit 1: a norm of the rotation map was below
+1e-8 and clamped)."""
+
+MAX_ANCHORS = 64
+ROTATION_WIDTHS = (4, 6)
+
+
+def _check_rotation_loss(confidence, y, label, R_target, w):
+    """Everything rotation_loss refuses, decided on the host from metadata alone (a host label's values included) -> (b, A, nr)."""
+    for name, t in (("confidence", confidence), ("y", y), ("label", label), ("R_target", R_target)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if confidence.dim() != 3 or confidence.shape[1] != confidence.shape[2] or not 1 <= confidence.shape[1] <= MAX_ANCHORS:
+        raise ValueError(f"confidence must be [b, A, A] (target anchor, source anchor) with 1 <= A <= {MAX_ANCHORS}, got "
+                         f"{tuple(confidence.shape)}")
+    b, A = confidence.shape[0], confidence.shape[1]
+    if b < 1:
+        raise ValueError("the loss is a mean over b * A rows and needs b >= 1 pairs, got 0")
+    if y.dim() != 4 or y.shape[0] != b or y.shape[1] not in ROTATION_WIDTHS or tuple(y.shape[2:]) != (A, A):
+        raise ValueError(f"y must be [{b}, 4 | 6, {A}, {A}], got {tuple(y.shape)}")
+    if tuple(label.shape) != (b, A):
+        raise ValueError(f"label must be [{b}, {A}], got {tuple(label.shape)}")
+    if tuple(R_target.shape) != (b, A, 3, 3):
+        raise ValueError(f"R_target must be [{b}, {A}, 3, 3], got {tuple(R_target.shape)}")
+    for name, t in (("confidence", confidence), ("y", y)):
+        if not t.is_floating_point():
+            raise TypeError(f"{name} must be a floating-point tensor, got {t.dtype}")
+    if label.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"label must be torch.int32 or torch.int64, got {label.dtype}")
+    if R_target.dtype != torch.float32:
+        raise TypeError(f"R_target must be torch.float32, got {R_target.dtype}")
+    w = float(w)
+    if w != w or w in (float("inf"), float("-inf")):
+        raise ValueError(f"w must be finite, got {w}")
+    # a host label (a loader's) is range-checked here and uploaded by the caller; checking a device label would synchronise:
+    # the kernels check it themselves and report a value outside 0..A-1 in bit 0 of row_flags
+    if not label.is_cuda and not (0 <= int(label.min()) and int(label.max()) < A):
+        raise ValueError(f"label must lie in 0..{A - 1}")
+    for name, t in (("confidence", confidence), ("y", y), ("R_target", R_target)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+    return b, A, y.shape[1]
+
+
+class _RotationLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wts, y, label, R_target, w):
+        b, nr, A = y.shape[0], y.shape[1], y.shape[2]
+        f32, i32 = dict(dtype=torch.float32, device=wts.device), dict(dtype=torch.int32, device=wts.device)
+        row_ce, row_l2, sel_R = torch.empty((b, A), **f32), torch.empty((b, A), **f32), torch.empty((b, A, 3, 3), **f32)
+        preds, row_flags = torch.empty((b, A), **i32), torch.empty((b, A), **i32)
+        scalars = torch.empty(4, **f32)
+        p = _lib.dev_ptr
+        _lib.check(_lib.get_lib().epn_rotation_loss_f32(
+            p(wts, "confidence"), p(y, "y"), p(label, "label", torch.int32), p(R_target, "R_target"), b, A, nr, w,
+            p(row_ce, "row_ce"), p(row_l2, "row_l2"), p(preds, "preds", torch.int32), p(row_flags, "row_flags", torch.int32),
+            p(sel_R, "sel_R"), p(scalars, "scalars"), _lib.stream_of(wts)), "rotation_loss")
+        ctx.save_for_backward(wts, y, label, R_target, row_flags)
+        ctx.w = w
+        ctx.set_materialize_grads(False)                    # no zero fills for the outputs nobody differentiates
+        loss, cls_loss, reg, r_acc = scalars.unbind(0)
+        ctx.mark_non_differentiable(cls_loss, reg, r_acc, preds, row_ce, row_l2, row_flags, sel_R)
+        return loss, cls_loss, reg, r_acc, preds, row_ce, row_l2, row_flags, sel_R
+
+    @staticmethod
+    def backward(ctx, g_loss, *unused):
+        if g_loss is None:
+            return None, None, None, None, None
+        wts, y, label, R_target, row_flags = ctx.saved_tensors
+        b, nr, A = y.shape[0], y.shape[1], y.shape[2]
+        upstream = g_loss.reshape(1).to(torch.float32).contiguous()
+        dwts, dy = torch.empty_like(wts), torch.empty_like(y)
+        p = _lib.dev_ptr
+        _lib.check(_lib.get_lib().epn_rotation_loss_bwd_f32(
+            p(upstream, "upstream"), p(wts, "confidence"), p(y, "y"), p(label, "label", torch.int32), p(R_target, "R_target"),
+            p(row_flags, "row_flags", torch.int32), b, A, nr, ctx.w, p(dwts, "dwts"), p(dy, "dy"), _lib.stream_of(wts)),
+            "rotation_loss_bwd")
+        return dwts, dy, None, None, None
+
+
+def rotation_loss_rows(confidence, y, label, R_target, w=10.0):
+    """rotation_loss with the selected rotations as well -> (RotationLossResult, sel_R f32 [b,A,3,3]: the rotation map of
+    y[p,:,label[p,a],a], zero where bit 0 of row_flags is set; not differentiable)."""
+    _check_rotation_loss(confidence, y, label, R_target, w)
+    # the head hands out channels-last y, under autocast bf16: the conversion is torch's, and the gradient flows back through it
+    wts, yc = confidence.float().contiguous(), y.float().contiguous()
+    label = label.to(device=wts.device, dtype=torch.int32).contiguous()
+    R_target = R_target.detach().contiguous()
+    _lib.same_device(wts, yc, label, R_target)
+    out = _RotationLoss.apply(wts, yc, label, R_target, float(w))
+    return RotationLossResult(*out[:8]), out[8]
+
+
+def rotation_loss(confidence, y, label, R_target, w=10.0):
+    """(confidence [b,A,A] (target anchor, source anchor) and y [b,4|6,A,A]: RegSO3ConvModel.forward's outputs, A <= 64; label
+    int32 / int64 [b,A] and R_target f32 [b,A,3,3]: label_relative_rotation's outputs; w: the weight of the L2 term) ->
+    RotationLossResult.  The alignment branch of the reference's MultiTaskDetectionLoss.forward (vgtk/vgtk/loss.py:140-181):
+    cross-entropy over the target-anchor axis of confidence taken as logits, plus w times the mean squared difference between
+    R_target and the rotation map (quaternion for 4 rows of y, Gram-Schmidt for 6) of y at the labelled target anchor.
+    Specification: include/epn_so3conv.h (epn_rotation_loss_f32 and its backward); fp64 inside, two launches
+    forward, one backward, nothing synchronises.  loss.backward() reaches confidence and y; everything else is for logging.
+    Label range: a HOST label is checked against 0..A-1 here and uploaded; a DEVICE label is not (that would synchronise): a value
+    outside 0..A-1 there sets bit 0 of that row's row_flags, and the row counts as zero in both sums and in the gradient."""
+    return rotation_loss_rows(confidence, y, label, R_target, w)[0]
 
 
 def _check_interp(feature, T, anchors, sigma):

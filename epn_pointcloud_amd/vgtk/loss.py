@@ -15,7 +15,21 @@ Same constructor, same forward signature, same return shapes.  What differs, on 
     formed; gt_idx (upstream builds arange(N) on opt.device in every forward, to compare with its top-1 indices) is NOT either:
     the kernel counts nn_idx[i] == i itself, and opt.device is read only if present.
   * _forward_attention is left out: upstream it raises for every loss type except 'no_reg', its entropy term never enters
-    the loss, and forward() never calls it."""
+    the loss, and forward() never calls it.
+
+And of vgtk/vgtk/loss.py:MultiTaskDetectionLoss (:94-210), the loss SPConvNets/trainer_modelnetRotation.py trains the rotation
+network with, on the kernels of csrc/rotation_loss.hip and csrc/rotation_decode.hip (losses.rotation_loss,
+alignment.decode_rotation).  Same constructor, same forward signature, the same five return values.
+What differs, on purpose:
+  * Only the alignment branch (:140-181) is served: a 2-d label with gt_T, which is what the shipped trainer always passes
+    (trainer_modelnetRotation.py:94, :112).  The single-anchor branch (na == 1) and the canonical-regression branch (gt_T None
+    or a 1-d label) raise NotImplementedError.
+  * fp64 arithmetic inside, one rounding per output; the most confident target anchor is the LOWEST index on a tie (torch.max
+    leaves that open).
+  * A device label is not range-checked on the host (torch's cross-entropy asserts on the device): an entry outside 0..A-1
+    counts as zero in both terms and in the gradient, and is reported in bit 0 of `row_flags`, kept on the module with `preds`.
+  * cls_loss, the L2 term and r_acc are logging values without a gradient; the angular error comes from the chordal mean's
+    Jacobi projection instead of torch.svd (3.1b)."""
 import torch
 import torch.nn as nn
 
@@ -71,3 +85,40 @@ class TripletBatchLoss(nn.Module):
         if knn != losses.KNN:
             raise ValueError(f"the anchor interpolation blends {losses.KNN} neighbours, got knn = {knn}")
         return losses.interpolate_anchor_features(feature, T, self.anchors, sigma)
+
+
+class MultiTaskDetectionLoss(nn.Module):
+    def __init__(self, anchors, nr=4, w=10, threshold=1.0):
+        """anchors f32 [A,3,3], A <= 64, on the device the head's outputs live on (kept as a plain attribute, as upstream); nr
+        = 4 (quaternion) or 6 (two columns) rows of y; w weighs the L2 term; threshold is read by the canonical branch only and
+        is accepted for the signature."""
+        super(MultiTaskDetectionLoss, self).__init__()
+        self.anchors = anchors
+        self.nr = nr
+        assert nr == 4 or nr == 6
+        self.w = w
+        self.threshold = threshold
+        self.iter_counter = 0
+
+    def forward(self, wts, label, y, gt_R, gt_T=None):
+        """(wts [b,A,A]: the confidence as logits over the target anchors (dim 1) per source anchor; label int [b,A]: the target
+        anchor of every source anchor; y [b,nr,A,A]; gt_R f32 [b,A,3,3]: the relative rotation to regress per source anchor; gt_T
+        f32 [b,3,3]: the ground-truth rotation) -> (loss, cls_loss, w * l2_loss, r_acc, angular error [b] in radians)."""
+        b, na = wts.shape[0], wts.shape[1]
+        if na == 1:
+            raise NotImplementedError("MultiTaskDetectionLoss: the single-anchor branch (na == 1, vgtk/vgtk/loss.py:131-139) is "
+                                      "not implemented; only the alignment branch is")
+        if gt_T is None or label.ndimension() != 2:
+            raise NotImplementedError("MultiTaskDetectionLoss: the canonical-regression branch (gt_T None or a 1-d label, "
+                                      "vgtk/vgtk/loss.py:183-205) is not implemented; only the alignment branch (2-d label with "
+                                      "gt_T) is")
+        if y.shape[1] != self.nr:
+            raise ValueError(f"y has {y.shape[1]} rows, the loss was built for nr = {self.nr}")
+        from .. import alignment                              # imports this package's functional: not at module level
+        wts = wts.view(b, na, na)
+        r = losses.rotation_loss(wts, y, label, gt_R, self.w)
+        self.preds, self.row_flags = r.preds, r.row_flags
+        err = alignment.decode_rotation(wts, y, self.anchors, gt=gt_T).err
+        if self.training:
+            self.iter_counter += 1
+        return r.loss, r.cls_loss, r.reg, r.r_acc, err

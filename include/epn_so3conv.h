@@ -295,6 +295,49 @@ int epn_rotation_decode_f32(const float *wts, const float *y, const float *ancho
                             int b, int A, int nr, float *pred_R, int32_t *preds, float *conf, float *margin, float *pred_Rs,
                             int32_t *hits, float *err, epn_stream_t stream);
 
+/* The rotation network's training loss: the alignment branch of MultiTaskDetectionLoss.forward (vgtk/vgtk/loss.py:140-181,
+ * with CrossEntropyLoss :18-30 and batched_select_anchor :77-92) and its backward (csrc/rotation_loss.hip).
+ * All tensors are contiguous device memory, float or int32: wts f32[b,A,A] (target anchor t, source anchor a), y f32[b,nr,A,A],
+ * label i32[b,A], R_target f32[b,A,3,3] (the reference's gt_R: epn_rotation_labels_f32's R_target), 1 <= A <= 64, nr = 4 or 6,
+ * w the weight of the L2 term.  Arithmetic is fp64 on the fp32 inputs and every output is rounded once to fp32.  No workspace, no
+ * atomics, no host synchronisation (the calls can be captured into a HIP graph); every sum runs in a fixed order, so two runs
+ * are bitwise equal.
+ * Refusals, decided before any HIP runtime call: EPN_EINVAL for b < 0, A outside 1..64, nr not 4 or 6, a non-finite w; then
+ * b == 0 succeeds and launches nothing; then EPN_ENULL for a pointer that is NULL (all are required).
+ *
+ * epn_rotation_loss_f32: for every pair p and source anchor a (a "row"), with L = label[p,a]:
+ *     row_flags bit 0: L lies outside 0..A-1.  Such a row is never used as an address: its row_ce and row_l2 are 0, its sel_R
+ *               is zero, bit 1 is clear and it contributes zero gradient.  It stays in the divisors below.
+ *     preds     = arg max over t of wts[p,t,a], fp32 comparison, the lowest t on a tie: epn_rotation_decode_f32's rule, so
+ *               the two entries agree on every input
+ *     row_ce    = m + log(sum_t exp(wts[p,t,a] - m)) - wts[p,L,a], m the maximum over t, t ascending: torch.nn.CrossEntropyLoss
+ *               on wts as logits with the class axis at dim 1, as the reference applies it
+ *     sel_R     = the rotation map of y[p,:,L,a], exactly as specified for epn_rotation_decode_f32 (one device function serves
+ *               both): nr = 4 the quaternion formula, nr = 6 the Gram-Schmidt form, n(v) = v / max(|v|, 1e-8)
+ *     row_flags bit 1: a norm entering that map (nr = 4: |q|; nr = 6: |y[0:3]| or |x cross y[3:6]|) was below 1e-8
+ *     row_l2    = sum_ij (R_target[p,a,i,j] - sel_R[p,a,i,j])^2 on the unrounded sel_R, added in row-major order
+ *   -> row_ce, row_l2 f32[b,A], preds, row_flags i32[b,A], sel_R f32[b,A,3,3] and scalars f32[4] = (loss, cls_loss, reg, r_acc),
+ *   the first four values of the reference's return tuple:
+ *     cls_loss = sum row_ce / (b A);  reg = w sum row_l2 / (9 b A);  loss = cls_loss + reg;  r_acc = #{preds == label} / (b A)
+ *   The sums run in fp64 over the ROUNDED per-row outputs (thread i of one workgroup adds rows i, i + 256, ... ascending, then
+ *   a fixed tree); cls_loss, reg and their fp64 sum are each rounded once.  Two launches; one wave per pair, lane a owns
+ *   source anchor a.
+ *
+ * epn_rotation_loss_bwd_f32: upstream f32[1] (the gradient of scalars[0], on the device), the forward's inputs and its row_flags
+ *   -> dwts f32[b,A,A], dy f32[b,nr,A,A], EVERY element written (zeros explicitly: the caller needs no memset).  With g = upstream:
+ *     dwts[p,t,a]  = g / (b A) (softmax_t(wts[p,.,a]) - [t == L]);  0 for every t of a row with bit 0 set
+ *     dy[p,:,t,a]  = 0 for t != L;  dy[p,:,L,a] = J^T vec(G), G = g 2 w / (9 b A) (sel_R - R_target), J the Jacobian of the
+ *                    rotation map at y[p,:,L,a]: through v / |v| where the norm was >= 1e-8, (I - u u^T) / |v| with u = v / |v|;
+ *                    through v / 1e-8 where the clamp was active (what autograd makes of torch.max(norm, 1e-8))
+ *   The softmax and sel_R are recomputed from the inputs in fp64 (the fp32 sel_R is not read).  The label is range-checked on
+ *   the device again before it is used as an address.  One launch. */
+int epn_rotation_loss_f32(const float *wts, const float *y, const int32_t *label, const float *R_target, int b, int A, int nr,
+                          double w, float *row_ce, float *row_l2, int32_t *preds, int32_t *row_flags, float *sel_R,
+                          float *scalars, epn_stream_t stream);
+int epn_rotation_loss_bwd_f32(const float *upstream, const float *wts, const float *y, const int32_t *label,
+                              const float *R_target, const int32_t *row_flags, int b, int A, int nr, double w, float *dwts,
+                              float *dy, epn_stream_t stream);
+
 /* The descriptor network's training loss: batch-hard triplet mining and the anchor interpolation of its equivariance term
  * (csrc/triplet_loss.hip).  All tensors are contiguous device memory, float or int32.  Arithmetic is fp64 on
  * the fp32 inputs and every output is rounded once to fp32.  No workspace, no atomics, no host synchronisation (the calls can
