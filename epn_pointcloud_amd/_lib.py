@@ -63,6 +63,7 @@ EXPORTS = [
     "epn_ransac_register_workspace_bytes", "epn_ransac_register_f64",
     "epn_triplet_batch_hard_f32", "epn_triplet_batch_hard_bwd_f32", "epn_anchor_interp_f32", "epn_anchor_interp_bwd_f32",
     "epn_rotation_loss_f32", "epn_rotation_loss_bwd_f32",
+    "epn_modelnet_batch_f32",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -350,6 +351,10 @@ def get_lib():
     # scalars), (upstream, wts, y, label, R_target, row_flags, b, A, nr, w, dwts, dy)
     lib.epn_rotation_loss_f32.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.epn_rotation_loss_bwd_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cd, _vp, _vp, _vp]
+    # ModelNet batches: (points, m, offsets, b, ids, n_sample, seed, key_bits, rot_mode, R_in, anchors, A, pc_out, pc_plain, idx, R,
+    # R_label, R_res, status)
+    lib.epn_modelnet_batch_f32.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, ctypes.c_uint64, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

@@ -603,3 +603,18 @@ extern "C" int epn_intra_so3conv_bwd_weight_f32(const float *feats_cl, const flo
     return launch_intra_bwd_weight_generic(feats_cl, grad_out_cl, intra_idx, (size_t)b * p, na, kn, cin, cout, grad_W,
                                            st);
 }
+
+// ModelNet training batches (modelnet_batch.hip): every argument is checked before the first HIP runtime call
+extern "C" int epn_modelnet_batch_f32(const float *points, int m, const int32_t *offsets, int b, const int64_t *ids,
+                                      int n_sample, uint64_t seed, int key_bits, int rot_mode, const float *R_in,
+                                      const float *anchors, int A, float *pc_out, float *pc_plain, int32_t *idx, float *R,
+                                      int32_t *R_label, float *R_res, int32_t *status, epn_stream_t stream) {
+    if (b < 0 || m < 0 || n_sample < 1 || n_sample > 8192 || key_bits < 1 || key_bits > 32) return EPN_EINVAL;
+    if (rot_mode < 0 || rot_mode > 2 || (rot_mode == 2 && !R_in)) return EPN_EINVAL;
+    if (anchors && (A < 1 || A > 64)) return EPN_EINVAL;
+    if (b == 0) return 0;
+    if (!offsets || !pc_out || !idx || !R || !status || (m > 0 && !points)) return EPN_EINVAL;
+    if (anchors && (!R_label || !R_res)) return EPN_EINVAL;
+    return launch_modelnet_batch(points, m, offsets, b, ids, n_sample, seed, key_bits, rot_mode, R_in, anchors, A, pc_out,
+                                 pc_plain, idx, R, R_label, R_res, status, epn_stream(stream));
+}

@@ -135,5 +135,10 @@ int launch_intra_bwd_data_mfma(const float *dOut, const int32_t *inv_idx, const 
                                int kn, int cin, int cout, float *dF, float *ws, hipStream_t st);
 int launch_intra_bwd_weight_mfma(const float *feats, const float *dOut, const int32_t *iidx, int b, int p, int na,
                                  int kn, int cin, int cout, float *dW, hipStream_t st);
+// modelnet_batch.hip: the arguments of epn_modelnet_batch_f32, already checked
+int launch_modelnet_batch(const float *points, int m, const int32_t *offsets, int b, const int64_t *ids, int n_sample,
+                          uint64_t seed, int key_bits, int rot_mode, const float *R_in, const float *anchors, int A,
+                          float *pc_out, float *pc_plain, int32_t *idx, float *R, int32_t *R_label, float *R_res, int32_t *status,
+                          hipStream_t st);
 
 }  // namespace epn

@@ -20,28 +20,19 @@
 //              the exact threshold key T and the number t of key == T members to take (the lowest i win)
 //   emit       compaction in ascending index: 64-bit ballot + popcount inside a wave, one LDS exchange (one barrier, two slot
 //              sets) across the four waves, a running base across chunks; key == T members are admitted while their rank
-//              among the ties is below t
+//              among the ties is below t  (the search and this step: key_select.h, shared with modelnet_batch.hip)
 //   upsample   slots >= count copy slots < count of the same row back after a workgroup barrier
 // Distances and keys are recomputed in every pass (Philox only for in-radius lanes): no [k, n] workspace.  Every loop is
 // bounded by n or n_sample; no workgroup talks to another, no global atomics, no spin: the result is bitwise repeatable.
 #include <cmath>
 
 #include "epn_common.h"
-#include "philox.h"
+#include "key_select.h"
 
 namespace {
 
-constexpr int PT = 256;            // threads per workgroup
-constexpr int PW = PT / 64;        // waves
-constexpr int PBINS = 2048;        // histogram bins: 11 + 11 + 10 key bits over the three levels
-constexpr int PBT = PBINS / PT;    // bins a thread owns in the search
-
-struct PatchShared {
-    unsigned hist[PBINS];
-    unsigned wsum[PW];
-    unsigned found[2];             // (bucket, members still to take inside it)
-    unsigned slots[2][PW][2];      // emit: (selected below T, ties) per wave, two sets -> one barrier per chunk
-};
+using namespace epn_keysel;        // PT, search_hist, emit_step: the selection shared with modelnet_batch.hip
+using PatchShared = Shared;
 
 __device__ __forceinline__ bool in_radius(const float *__restrict__ pc, unsigned i, float qx, float qy, float qz, float r2,
                                           float &px, float &py, float &pz) {
@@ -52,48 +43,7 @@ __device__ __forceinline__ bool in_radius(const float *__restrict__ pc, unsigned
 }
 
 __device__ __forceinline__ unsigned patch_key(unsigned i, unsigned long long Q, unsigned long long seed, int key_bits) {
-    return epn::philox::philox4x32_10((unsigned long long)i, Q, seed).w[0] >> (32 - key_bits);
-}
-
-__device__ __forceinline__ void clear_hist(PatchShared &sh) {
-    for (int b = threadIdx.x; b < PBINS; b += PT) sh.hist[b] = 0u;
-}
-
-// The histogram's total and, when 1 <= need <= total, the bucket B with below(B) < need <= below(B) + hist[B] and
-// need - below(B).  Every thread calls it (barriers inside) and gets the same three values.
-__device__ __forceinline__ unsigned search_hist(PatchShared &sh, unsigned need, unsigned &bucket, unsigned &rest) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __syncthreads();                                   // the pass's LDS atomics are done
-    unsigned h[PBT], own = 0u;
-#pragma unroll
-    for (int b = 0; b < PBT; ++b) { h[b] = sh.hist[PBT * tid + b]; own += h[b]; }
-    unsigned incl = own;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const unsigned o = __shfl_up(incl, s, 64);
-        incl += lane >= s ? o : 0u;
-    }
-    if (lane == 63) sh.wsum[wave] = incl;
-    if (tid == 0) { sh.found[0] = 0u; sh.found[1] = 0u; }
-    __syncthreads();
-    unsigned below = incl - own, total = 0u;
-#pragma unroll
-    for (int w = 0; w < PW; ++w) {
-        below += w < wave ? sh.wsum[w] : 0u;
-        total += sh.wsum[w];
-    }
-    if (below < need && need <= below + own) {         // exactly one thread when 1 <= need <= total
-#pragma unroll
-        for (int b = 0; b < PBT; ++b) {
-            if (below < need && need <= below + h[b]) { sh.found[0] = (unsigned)(PBT * tid + b); sh.found[1] = need - below; }
-            below += h[b];
-        }
-    }
-    __syncthreads();
-    bucket = sh.found[0];
-    rest = sh.found[1];
-    __syncthreads();                                   // found / wsum / hist may be rewritten by the caller
-    return total;
+    return key_of(i, Q, seed, key_bits);
 }
 
 __global__ __launch_bounds__(PT) void radius_patches_kernel(const float *__restrict__ pc, int n, const float *__restrict__ kpts,
@@ -101,7 +51,7 @@ __global__ __launch_bounds__(PT) void radius_patches_kernel(const float *__restr
                                                             unsigned long long seed, int key_bits, int center, float scale,
                                                             int32_t *idx, int32_t *__restrict__ counts, float *patches) {
     __shared__ PatchShared sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const unsigned q = blockIdx.x, un = (unsigned)n;
     const unsigned long long Q = kpt_row0 + q;
     const float qx = kpts[(size_t)3 * q], qy = kpts[(size_t)3 * q + 1], qz = kpts[(size_t)3 * q + 2];
@@ -160,10 +110,8 @@ __global__ __launch_bounds__(PT) void radius_patches_kernel(const float *__restr
 
     // ---- emit: ascending index; `less` lanes always, `tie` lanes while their rank among the ties is below `take`
     const float cx = center ? qx : 0.0f, cy = center ? qy : 0.0f, cz = center ? qz : 0.0f;
-    const unsigned long long below_lane = (1ull << lane) - 1ull;
-    unsigned out_base = 0u, tie_base = 0u;             // members written / ties seen in the chunks so far
-    int set = 0;
-    for (unsigned base = 0; base < un; base += PT, set ^= 1) {
+    Emit em;
+    for (unsigned base = 0; base < un; base += PT) {
         const unsigned i = base + tid;
         bool less = false, tie = false;
         if (i < un && in_radius(pc, i, qx, qy, qz, r2, px, py, pz)) {
@@ -175,35 +123,13 @@ __global__ __launch_bounds__(PT) void radius_patches_kernel(const float *__restr
                 tie = key == T;
             }
         }
-        const unsigned long long mless = __ballot(less), mtie = __ballot(tie);
-        if (lane == 0) { sh.slots[set][wave][0] = (unsigned)__popcll(mless); sh.slots[set][wave][1] = (unsigned)__popcll(mtie); }
-        __syncthreads();
-        unsigned less_before = 0u, ties_before = 0u, less_all = 0u, ties_all = 0u;
-#pragma unroll
-        for (int w = 0; w < PW; ++w) {
-            const unsigned a = sh.slots[set][w][0], b = sh.slots[set][w][1];
-            less_before += w < wave ? a : 0u;
-            ties_before += w < wave ? b : 0u;
-            less_all += a;
-            ties_all += b;
+        unsigned pos;
+        if (emit_step(sh, em, less, tie, take, pos) && pos < (unsigned)n_sample) {
+            irow[pos] = (int32_t)i;
+            prow[3 * (size_t)pos] = __fmul_rn(__fsub_rn(px, cx), scale);
+            prow[3 * (size_t)pos + 1] = __fmul_rn(__fsub_rn(py, cy), scale);
+            prow[3 * (size_t)pos + 2] = __fmul_rn(__fsub_rn(pz, cz), scale);
         }
-        // ties admitted so far (earlier chunks: tie_base of them, capped by take) and in this chunk's earlier waves
-        const unsigned room = take > tie_base ? take - tie_base : 0u;            // ties this chunk may still admit
-        const unsigned adm_before = ties_before < room ? ties_before : room;
-        const unsigned rank = ties_before + (unsigned)__popcll(mtie & below_lane);   // among this chunk's ties
-        const bool sel = less || (tie && rank < room);
-        const unsigned long long msel = __ballot(sel);
-        if (sel) {
-            const unsigned pos = out_base + less_before + adm_before + (unsigned)__popcll(msel & below_lane);
-            if (pos < (unsigned)n_sample) {
-                irow[pos] = (int32_t)i;
-                prow[3 * (size_t)pos] = __fmul_rn(__fsub_rn(px, cx), scale);
-                prow[3 * (size_t)pos + 1] = __fmul_rn(__fsub_rn(py, cy), scale);
-                prow[3 * (size_t)pos + 2] = __fmul_rn(__fsub_rn(pz, cz), scale);
-            }
-        }
-        out_base += less_all + (ties_all < room ? ties_all : room);
-        tie_base += ties_all;
     }
 
     // ---- upsample (1 < count < n_sample): draw with replacement from the row's first `count` slots

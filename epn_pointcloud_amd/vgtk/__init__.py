@@ -1,6 +1,7 @@
 """Mirror of the reference package `vgtk` (vgtk/vgtk/__init__.py:1-13), hot-path subset:
 functional, point3d, pc, spconv, so3conv, utils, loss (TripletBatchLoss, the 3DMatch trainer's loss, and MultiTaskDetectionLoss,
-the rotation trainer's, alignment branch) and the extension namespace `cuda`.
+the rotation trainer's, alignment branch) and the extension namespace `cuda`.  pc also carries the device form of the ModelNet
+loaders' per-sample work (pc.modelnet_batch, pc.modelnet_alignment_batch: resample, normalise, rotate, label).
 Out of scope: app (trainer/logger), the classification losses (CrossEntropyLoss,
 AttentionCrossEntropyLoss: plain torch upstream), transform, mesh, voxel (upstream's package of that name is
 empty; the voxel-grid downsampling the reference takes from open3d is pc.voxel_down_sample)."""

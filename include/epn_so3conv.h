@@ -127,6 +127,54 @@ int epn_radius_patches_f32(const float *pc, int n, const float *kpts, int k, int
                            uint64_t seed, int key_bits, int center, float scale, int32_t *idx, int32_t *counts,
                            float *patches, epn_stream_t stream);
 
+/* ModelNet training batches: a ragged set of raw clouds -> the [b, n_sample, 3] tensor, the rotations and the anchor labels
+ * that the classification and rotation networks and their losses take.  Replaces the host path of the reference's ModelNet
+ * loaders (SPConvNets/datasets/modelnet40.py:50-80 and :115-160), which per sample, in a DataLoader worker, resamples with
+ * np.random.choice (pctk.uniform_resample_np, vgtk/vgtk/pc/sample.py:16-36), centres and scales (p3dtk.normalize_np,
+ * vgtk/vgtk/point3d/normalize.py:30-34), rotates by scipy's Rotation.random (pctk.rotate_point_cloud,
+ * vgtk/vgtk/pc/augmentation.py:58-89) and labels the rotation against the anchors (rotation_distance_np,
+ * vgtk/vgtk/functional/rotation.py:350-369).  Those draws cannot be reproduced; this is the library's own deterministic form
+ * of the same semantics (csrc/modelnet_batch.hip).
+ *   points f32[m,3]: the clouds of a batch, concatenated; offsets i32[b+1] ON THE DEVICE: cloud c is rows offsets[c] ..
+ *   offsets[c+1]-1, n_c of them; ids i64[b] on the device or NULL (id_c = c): the sample's identity, e.g. dataset index +
+ *   epoch * dataset length.  With Q = id_c, every random draw of cloud c depends on (seed, Q) only -- never on c, on b or on
+ *   the other clouds -- so a shuffled loader reproduces.
+ *   -> pc_out f32[b,n_sample,3], pc_plain f32[b,n_sample,3] or NULL, idx i32[b,n_sample] (rows within the cloud), R f32[b,3,3],
+ *      R_label i32[b], R_res f32[b,3,3], status i32[b]; every element is written on every call.
+ *   selection     exactly the rule of epn_radius_patches_f32 with every point a member:
+ *                 key(i) = word0(Philox4x32-10(ctr_lo = i, ctr_hi = Q, key = seed)) >> (32 - key_bits);
+ *                 n_c >= n_sample: the n_sample indices smallest in (key, i), written in ascending i (n_c == n_sample is the
+ *                 identity: the reference's test mode); 1 <= n_c < n_sample: slots 0..n_c-1 = 0..n_c-1 and slot j >= n_c is
+ *                 word1(Philox4x32-10(ctr_lo = j, ctr_hi = Q, key = seed)) mod n_c.
+ *   normalisation fp64 inside: c = the mean of the n_sample selected rows, duplicates counted (the reference normalises after
+ *                 resampling); s = the largest |p - c| over them; p' = (p - c) / s.  pc_plain = p' rounded once.
+ *   rotation      rot_mode 0: R = I.  rot_mode 2: R = R_in[c] (f32[b,3,3]: the reference's testR files).  rot_mode 1:
+ *                 w = Philox4x32-10(ctr_lo = 2^32, ctr_hi = Q, key = seed), a counter no point index reaches;
+ *                 u_k = (w[k] + 0.5) / 2^32, k = 0, 1, 2; Shoemake's quaternion x = sqrt(1-u0) sin(2 pi u1),
+ *                 y = sqrt(1-u0) cos(2 pi u1), z = sqrt(u0) sin(2 pi u2), w = sqrt(u0) cos(2 pi u2); the standard
+ *                 unit-quaternion matrix in fp64, rounded once to fp32: that fp32 matrix is R.
+ *                 pc_out = R p' (the reference's convention, augmentation.py:87) in fp64 from the ROUNDED R, rounded once: the
+ *                 returned R is exactly the rotation that was applied.
+ *   anchor label  anchors f32[A,3,3], 1 <= A <= 64, or NULL (then R_label and R_res may be NULL and are not written).
+ *                 R_label = arg max_i tr(A_i^T R) from the rounded R and the fp32 anchors, the nine products accumulated in fp64
+ *                 in row-major order, the lowest i on a tie; R_res = A_label^T R in fp64, rounded once (the diff_r[label]
+ *                 that the reference's flag == 'rotation' path trains on).
+ *   status        bits 1, 2, 4, 8; the conditions exclude one another (a NaN extent is not == 0, an empty or badly delimited
+ *                 cloud has no extent), so a cloud carries one of them, the first that applies: 8 offsets[c] > offsets[c+1] or outside [0, m]; 1 an empty
+ *                 cloud; 4 a non-finite coordinate among the selected rows; 2 zero extent (s == 0; a one-point cloud is one);
+ *                 0 otherwise.  A cloud with a status reads nothing out of range; its pc_out, pc_plain and R_res are zeros
+ *                 and its idx is -1; its R is still drawn and its R_label computed.  Nothing asserts; no cloud affects another.
+ * Refusals, decided before any HIP runtime call, all EPN_EINVAL: b < 0, m < 0, n_sample outside 1..8192, key_bits outside
+ * 1..32, rot_mode outside 0..2, rot_mode 2 without R_in, anchors given with A outside 1..64; then b == 0 succeeds and launches
+ * nothing; then a required pointer that is NULL (offsets, pc_out, idx, R, status; points when m > 0; R_label and R_res when
+ * anchors is given).  One launch, one 256-thread workgroup per cloud, no workspace, no global atomics, no allocation, no host
+ * synchronisation (the call can be captured into a HIP graph and replayed after ids were rewritten in place); the centroid is
+ * summed in a fixed order: two calls are bitwise equal. */
+int epn_modelnet_batch_f32(const float *points, int m, const int32_t *offsets, int b, const int64_t *ids, int n_sample,
+                           uint64_t seed, int key_bits, int rot_mode, const float *R_in, const float *anchors, int A,
+                           float *pc_out, float *pc_plain, int32_t *idx, float *R, int32_t *R_label, float *R_res,
+                           int32_t *status, epn_stream_t stream);
+
 /* Descriptor matching: for every fragment pair of a scene, the exact nearest neighbour in descriptor space in both
  * directions, then the mutual check "tgt -> src -> tgt", the ground-truth transform and the inlier count.  Replaces the host
  * block of the reference's evaluation (SPConvNets/datasets/evaluation_3dmatch.py:77-100: two sklearn KDTrees, the mutual
