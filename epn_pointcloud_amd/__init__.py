@@ -7,6 +7,7 @@ Holds only what the path needs:
   ops.py     autograd Functions over the C ABI (channels-last feature tensors)
   matching.py  descriptor matching, the 3DMatch inlier ratio / recall and pairwise registration on the device (after models.describe)
   alignment.py  rotation decode, chordal mean and angular error on the device (after RegSO3ConvModel.forward)
+  classification.py  the classification trainer's evaluation loop on the device (after ClsSO3ConvModel.forward)
   data.py    ModelNet training batches on the device: resample, normalise, rotate, label (before the models' forward)
 
 `install_vgtk_alias()` registers the mirror under the reference's import names (`vgtk`,
@@ -31,13 +32,14 @@ _MATCHING = ("match_descriptors", "evaluate_fragment_pair", "evaluate_scene", "r
              "registration_errors", "registration_recall", "RegistrationResult")
 _ALIGNMENT = ("decode_rotation", "evaluate_alignment")
 _DATA = ("pack_clouds", "modelnet_batch", "modelnet_alignment_batch", "ModelNetBatch")
+_CLASSIFICATION = ("evaluate_classification",)
 
 
 def __getattr__(name):
     """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` / `.register_scene` /
     `.register_fragment_pair` / `.registration_errors` / `.registration_recall` (matching.py) and
     `.decode_rotation` / `.evaluate_alignment` (alignment.py) and `.pack_clouds` / `.modelnet_batch` /
-    `.modelnet_alignment_batch` (data.py), resolved on first use so that importing the package -- the
+    `.modelnet_alignment_batch` (data.py) and `.evaluate_classification` (classification.py), resolved on first use so that importing the package -- the
     build recipe does -- still needs no torch."""
     if name in _MATCHING:
         from . import matching
@@ -48,4 +50,7 @@ def __getattr__(name):
     if name in _DATA:
         from . import data
         return getattr(data, name)
+    if name in _CLASSIFICATION:
+        from . import classification
+        return getattr(classification, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -64,6 +64,7 @@ EXPORTS = [
     "epn_triplet_batch_hard_f32", "epn_triplet_batch_hard_bwd_f32", "epn_anchor_interp_f32", "epn_anchor_interp_bwd_f32",
     "epn_rotation_loss_f32", "epn_rotation_loss_bwd_f32",
     "epn_modelnet_batch_f32",
+    "epn_cls_loss_f32", "epn_cls_loss_bwd_f32", "epn_cls_tally_i32",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -355,6 +356,13 @@ def get_lib():
     # R_label, R_res, status)
     lib.epn_modelnet_batch_f32.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, ctypes.c_uint64, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp,
                                            _vp, _vp, _vp, _vp, _vp]
+    # classification loss and tallies: (logits, label, B, k, att, att_label, R, A, coef, three per-row outputs per set, scalars),
+    # (upstream, logits, label, flags, B, k, att, att_label, att_flags, R, A, coef, dlogits, datt),
+    # (pred, label, flags, att_pred, att_label, att_flags, B, k, A, confusion, anchor_table, totals)
+    lib.epn_cls_loss_f32.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.epn_cls_loss_bwd_f32.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]
+    lib.epn_cls_tally_i32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]
+    lib.epn_cls_tally_i32.restype = _ci
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):

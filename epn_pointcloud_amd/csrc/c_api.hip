@@ -618,3 +618,39 @@ extern "C" int epn_modelnet_batch_f32(const float *points, int m, const int32_t 
     return launch_modelnet_batch(points, m, offsets, b, ids, n_sample, seed, key_bits, rot_mode, R_in, anchors, A, pc_out,
                                  pc_plain, idx, R, R_label, R_res, status, epn_stream(stream));
 }
+
+// Classification loss and tallies (cls_loss.hip): every argument is checked before the first HIP runtime call.  Sizes first
+// (EPN_EINVAL), then pointers (EPN_ENULL); the attention set is absent as a whole (R == 0: its pointers are not looked at)
+static bool cls_rows_ok(int rows, int n) { return rows >= 1 && rows <= 65536 && n >= 1 && n <= 4096 && (long long)rows * n < (1LL << 31); }
+
+extern "C" int epn_cls_loss_f32(const float *logits, const int32_t *label, int B, int k, const float *att,
+                                const int32_t *att_label, int R, int A, const float *coef, float *row_ce, int32_t *pred,
+                                int32_t *flags, float *att_row_ce, int32_t *att_pred, int32_t *att_flags, float *scalars,
+                                epn_stream_t stream) {
+    if (!cls_rows_ok(B, k) || (R != 0 && !cls_rows_ok(R, A))) return EPN_EINVAL;
+    if (!logits || !label || !coef || !row_ce || !pred || !flags || !scalars) return EPN_ENULL;
+    if (R != 0 && (!att || !att_label || !att_row_ce || !att_pred || !att_flags)) return EPN_ENULL;
+    return launch_cls_loss(logits, label, B, k, att, att_label, R, A, coef, row_ce, pred, flags, att_row_ce, att_pred, att_flags,
+                           scalars, epn_stream(stream));
+}
+
+extern "C" int epn_cls_loss_bwd_f32(const float *upstream, const float *logits, const int32_t *label, const int32_t *flags, int B,
+                                    int k, const float *att, const int32_t *att_label, const int32_t *att_flags, int R, int A,
+                                    const float *coef, float *dlogits, float *datt, epn_stream_t stream) {
+    if (!cls_rows_ok(B, k) || (R != 0 && !cls_rows_ok(R, A))) return EPN_EINVAL;
+    if (!upstream || !logits || !label || !flags || !coef || !dlogits) return EPN_ENULL;
+    if (R != 0 && (!att || !att_label || !att_flags || !datt)) return EPN_ENULL;
+    return launch_cls_loss_bwd(upstream, logits, label, flags, B, k, att, att_label, att_flags, R, A, coef, dlogits, datt,
+                               epn_stream(stream));
+}
+
+extern "C" int epn_cls_tally_i32(const int32_t *pred, const int32_t *label, const int32_t *flags, const int32_t *att_pred,
+                                 const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
+                                 int32_t *anchor_table, int32_t *totals, epn_stream_t stream) {
+    if (B < 1 || B > 65536 || k < 1 || k > 4096) return EPN_EINVAL;
+    if (att_pred && (A < 1 || A > 4096)) return EPN_EINVAL;
+    if (!pred || !label || !flags || !confusion || !totals) return EPN_ENULL;
+    if (att_pred && (!att_flags || !anchor_table)) return EPN_ENULL;
+    return launch_cls_tally(pred, label, flags, att_pred, att_pred ? att_label : nullptr, att_flags, B, k, A, confusion,
+                            anchor_table, totals, epn_stream(stream));
+}

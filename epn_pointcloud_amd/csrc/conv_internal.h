@@ -140,5 +140,15 @@ int launch_modelnet_batch(const float *points, int m, const int32_t *offsets, in
                           uint64_t seed, int key_bits, int rot_mode, const float *R_in, const float *anchors, int A,
                           float *pc_out, float *pc_plain, int32_t *idx, float *R, int32_t *R_label, float *R_res, int32_t *status,
                           hipStream_t st);
+// cls_loss.hip: the arguments of epn_cls_loss_f32, epn_cls_loss_bwd_f32 and epn_cls_tally_i32, already checked
+int launch_cls_loss(const float *logits, const int32_t *label, int B, int k, const float *att, const int32_t *att_label, int R,
+                    int A, const float *coef, float *row_ce, int32_t *pred, int32_t *flags, float *att_row_ce,
+                    int32_t *att_pred, int32_t *att_flags, float *scalars, hipStream_t st);
+int launch_cls_loss_bwd(const float *upstream, const float *logits, const int32_t *label, const int32_t *flags, int B, int k,
+                        const float *att, const int32_t *att_label, const int32_t *att_flags, int R, int A, const float *coef,
+                        float *dlogits, float *datt, hipStream_t st);
+int launch_cls_tally(const int32_t *pred, const int32_t *label, const int32_t *flags, const int32_t *att_pred,
+                     const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
+                     int32_t *anchor_table, int32_t *totals, hipStream_t st);
 
 }  // namespace epn

@@ -12,6 +12,12 @@ anchor cross-entropy plus the L2 distance of the regressed relative rotations --
 trains with.  Specification: epn_rotation_loss_f32 and its backward; kernels: csrc/rotation_loss.hip.  Forward
 two launches, backward one, under the same rules.
 
+And the classification network's: classification_loss, the reference's CrossEntropyLoss and AttentionCrossEntropyLoss
+(loss.py:18-75) -- class cross-entropy blended with the cross-entropy of the anchor attention -- the loss
+SPConvNets/trainer_modelnet.py trains with, and classification_tally, the counting of its evaluation loop.  Specification:
+epn_cls_loss_f32, its backward and epn_cls_tally_i32; kernels: csrc/cls_loss.hip.  Forward two launches, backward
+one, tally one; the blend weights are read on the device.
+
 Shapes and dtypes are checked on the host before the device is touched: type, shape, dtype, then device."""
 import collections
 
@@ -228,6 +234,236 @@ def rotation_loss(confidence, y, label, R_target, w=10.0):
     Label range: a HOST label is checked against 0..A-1 here and uploaded; a DEVICE label is not (that would synchronise): a value
     outside 0..A-1 there sets bit 0 of that row's row_flags, and the row counts as zero in both sums and in the gradient."""
     return rotation_loss_rows(confidence, y, label, R_target, w)[0]
+
+
+ClsLossResult = collections.namedtuple(
+    "ClsLossResult", "loss cls_loss att_loss acc att_acc preds att_preds row_ce att_row_ce row_flags att_row_flags")
+ClsLossResult.__doc__ = """classification_loss's result: loss (f32 scalar, c_cls * cls_loss + c_att * att_loss; the only
+differentiable field), cls_loss and att_loss (the mean cross-entropy over the B class rows and over the R attention rows), acc and
+att_acc (share of rows whose arg max is the label) -- the five values AttentionCrossEntropyLoss.forward returns -- and per row:
+preds int32 [B] and att_preds int32 [B] or [B,C] (the arg max, the lowest index on a tie, -1 for a row with a non-finite logit),
+row_ce and att_row_ce f32, row_flags and att_row_flags int32 (bit 0: the label lies outside the row's classes and the row counts
+as zero; bit 1: the row holds a non-finite logit).  Without attention: att_loss = att_acc = 0 and the att_* rows are None."""
+
+MAX_CLASSES = 4096
+
+
+def _check_classification_loss(logits, label, attention, attention_label, coef):
+    """Everything classification_loss refuses, decided on the host from metadata alone (a host label's values included)."""
+    for name, t in (("logits", logits), ("label", label)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if (attention is None) != (attention_label is None):
+        raise TypeError("attention and attention_label come together: both tensors, or both None")
+    for name, t in (("attention", attention), ("attention_label", attention_label)):
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if not isinstance(coef, torch.Tensor):
+        if not isinstance(coef, (tuple, list)) or len(coef) != 2 or not all(isinstance(c, (int, float)) for c in coef):
+            raise TypeError(f"coef must be a pair of floats or a device float32 tensor of two elements, got {coef!r}")
+    if logits.dim() != 2 or not 1 <= logits.shape[0] <= MAX_ROWS or not 1 <= logits.shape[1] <= MAX_CLASSES:
+        raise ValueError(f"logits must be [B, k] with 1 <= B <= {MAX_ROWS} and 1 <= k <= {MAX_CLASSES}, got {tuple(logits.shape)}")
+    B, k = logits.shape
+    if tuple(label.shape) != (B,):
+        raise ValueError(f"label must be [{B}], got {tuple(label.shape)}")
+    if attention is not None:
+        if attention.dim() not in (2, 3) or attention.shape[0] != B or not 1 <= attention.shape[-1] <= MAX_CLASSES:
+            raise ValueError(f"attention must be [{B}, A] or [{B}, C, A] with 1 <= A <= {MAX_CLASSES}, got {tuple(attention.shape)}")
+        R = attention.numel() // attention.shape[-1]
+        if not 1 <= R <= MAX_ROWS:
+            raise ValueError(f"attention has {R} rows, one call takes 1..{MAX_ROWS}")
+        if tuple(attention_label.shape) != tuple(attention.shape[:-1]):
+            raise ValueError(f"attention_label must be {list(attention.shape[:-1])}, got {tuple(attention_label.shape)}")
+    if isinstance(coef, torch.Tensor) and (tuple(coef.shape) != (2,) or not coef.is_contiguous()):
+        # a strided view would have to be copied, and a captured step would then never see its later updates
+        raise ValueError(f"a coef tensor must be a contiguous [2] = (c_cls, c_att), got shape {tuple(coef.shape)}, stride "
+                         f"{tuple(coef.stride())}")
+    for name, t in (("logits", logits), ("attention", attention)):
+        if t is not None and not t.is_floating_point():
+            raise TypeError(f"{name} must be a floating-point tensor, got {t.dtype}")
+    for name, t in (("label", label), ("attention_label", attention_label)):
+        if t is not None and t.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{name} must be torch.int32 or torch.int64, got {t.dtype}")
+    if isinstance(coef, torch.Tensor):
+        if coef.dtype != torch.float32:
+            raise TypeError(f"a coef tensor must be torch.float32, got {coef.dtype}")
+    elif not all(c == c and c not in (float("inf"), float("-inf")) for c in map(float, coef)):
+        raise ValueError(f"coef must be finite, got {coef!r}")
+    # a host label (a loader's) is range-checked here and uploaded by the caller; checking a device label would synchronise:
+    # the kernels check it themselves and report a value outside the row's classes in bit 0 of the row's flags
+    for name, t, n in (("label", label, k), ("attention_label", attention_label, attention.shape[-1] if attention is not None else 0)):
+        if t is not None and not t.is_cuda and not (0 <= int(t.min()) and int(t.max()) < n):
+            raise ValueError(f"{name} must lie in 0..{n - 1}")
+    for name, t in (("logits", logits), ("attention", attention), ("coef", coef if isinstance(coef, torch.Tensor) else None)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+
+
+class _ClsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, label, att, att_label, coef):
+        B, k = logits.shape
+        R, A = (att.shape[0], att.shape[1]) if att is not None else (0, 0)
+        f32, i32 = dict(dtype=torch.float32, device=logits.device), dict(dtype=torch.int32, device=logits.device)
+        row_ce, preds, row_flags = torch.empty(B, **f32), torch.empty(B, **i32), torch.empty(B, **i32)
+        att_row_ce = att_preds = att_row_flags = None
+        if R:
+            att_row_ce, att_preds, att_row_flags = torch.empty(R, **f32), torch.empty(R, **i32), torch.empty(R, **i32)
+        scalars = torch.empty(5, **f32)
+        p = _lib.dev_ptr
+        _lib.check(_lib.get_lib().epn_cls_loss_f32(
+            p(logits, "logits"), p(label, "label", torch.int32), B, k, p(att, "attention"), p(att_label, "attention_label", torch.int32),
+            R, A, p(coef, "coef"), p(row_ce, "row_ce"), p(preds, "preds", torch.int32), p(row_flags, "row_flags", torch.int32),
+            p(att_row_ce, "att_row_ce"), p(att_preds, "att_preds", torch.int32), p(att_row_flags, "att_row_flags", torch.int32),
+            p(scalars, "scalars"), _lib.stream_of(logits)), "classification_loss")
+        ctx.save_for_backward(logits, label, row_flags, att, att_label, att_row_flags, coef)
+        ctx.set_materialize_grads(False)                    # no zero fills for the outputs nobody differentiates
+        loss, cls_loss, att_loss, acc, att_acc = scalars.unbind(0)
+        ctx.mark_non_differentiable(*(t for t in (cls_loss, att_loss, acc, att_acc, preds, att_preds, row_ce, att_row_ce, row_flags,
+                                                  att_row_flags) if t is not None))
+        return loss, cls_loss, att_loss, acc, att_acc, preds, att_preds, row_ce, att_row_ce, row_flags, att_row_flags
+
+    @staticmethod
+    def backward(ctx, g_loss, *unused):
+        if g_loss is None:
+            return None, None, None, None, None
+        logits, label, row_flags, att, att_label, att_row_flags, coef = ctx.saved_tensors
+        B, k = logits.shape
+        R, A = (att.shape[0], att.shape[1]) if att is not None else (0, 0)
+        upstream = g_loss.reshape(1).to(torch.float32).contiguous()
+        dlogits = torch.empty_like(logits)
+        datt = torch.empty_like(att) if R else None
+        p = _lib.dev_ptr
+        _lib.check(_lib.get_lib().epn_cls_loss_bwd_f32(
+            p(upstream, "upstream"), p(logits, "logits"), p(label, "label", torch.int32), p(row_flags, "row_flags", torch.int32), B, k,
+            p(att, "attention"), p(att_label, "attention_label", torch.int32), p(att_row_flags, "att_row_flags", torch.int32), R, A,
+            p(coef, "coef"), p(dlogits, "dlogits"), p(datt, "datt"), _lib.stream_of(logits)), "classification_loss_bwd")
+        return dlogits, None, datt, None, None
+
+
+def classification_loss(logits, label, attention=None, attention_label=None, coef=(1.0, 1.0)):
+    """(logits [B,k]: ClsSO3ConvModel.forward's first output; label int32 / int64 [B]; attention [B,A] with attention_label [B]
+    -- the network's second output and the loader's R_label -- or [B,C,A] with attention_label [B,C], one row per (b, c); coef =
+    (c_cls, c_att): a pair of floats, or a contiguous DEVICE float32 [2] tensor that is used in place, never copied) -> ClsLossResult.  The reference's
+    CrossEntropyLoss (attention None) and AttentionCrossEntropyLoss (vgtk/vgtk/loss.py:18-75) with the blend left to coef:
+    loss = c_cls * mean CE(logits, label) + c_att * mean CE(attention rows, attention_label).
+    Specification: include/epn_so3conv.h (epn_cls_loss_f32 and its backward); fp64 inside, two launches forward,
+    one backward, nothing synchronises.  loss.backward() reaches logits and attention; everything else is for logging.  The
+    kernels read coef on the device: a captured step replays with new blend weights after coef.copy_(...); a pair of floats is
+    uploaded by this call, which a capture does not allow -- pass the tensor there.
+    Label range: a HOST label is checked against the row's classes here and uploaded; a DEVICE label is not (that would
+    synchronise): a value outside them sets bit 0 of that row's flags, and the row counts as zero in the sums and in the gradient
+    while the means still divide by B and R.  torch's cross-entropy asserts on the device there, except for ignore_index = -100,
+    which it also takes out of the divisor: -100 is no exception here.  A row with a non-finite logit sets bit 1: its row_ce and
+    gradient are NaN (so is the mean) and its prediction is -1."""
+    _check_classification_loss(logits, label, attention, attention_label, coef)
+    # non-fp32 logits (a bf16 head): the conversion is torch's, and the gradient flows back through it
+    x = logits.float().contiguous()
+    dev = x.device
+    label = label.to(device=dev, dtype=torch.int32).contiguous()
+    att = att_label = None
+    if attention is not None:
+        att = attention.float().contiguous().reshape(-1, attention.shape[-1])
+        att_label = attention_label.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+    coef = coef.detach() if isinstance(coef, torch.Tensor) else torch.tensor([float(c) for c in coef], dtype=torch.float32,
+                                                                                         device=dev)
+    _lib.same_device(x, label, att, att_label, coef)
+    out = list(_ClsLoss.apply(x, label, att, att_label, coef))
+    if attention is not None and attention.dim() == 3:
+        for i in (6, 8, 10):
+            out[i] = out[i].view(attention.shape[:-1])
+    return ClsLossResult(*out)
+
+
+ClassificationTally = collections.namedtuple(
+    "ClassificationTally", "instance_acc class_acc attention_acc confusion anchor_table rows skipped")
+ClassificationTally.__doc__ = """ClassificationTables.result(): instance_acc (rows correct / rows seen), class_acc (float64 [k]:
+the diagonal of confusion over its row sums, NaN for a class never seen), attention_acc (attention rows correct / rows seen; NaN
+without attention labels), confusion int32 [k,k] at (label, prediction), anchor_table int32 [k,A] at (label, most attended anchor)
+or None, rows (seen) and skipped (flagged rows, left out of every count) -- host values."""
+
+
+class ClassificationTables:
+    """The int32 tables classification_tally adds into, on `device`, zeroed here: confusion [k,k], anchor_table [k,A] (None with
+    A = 0) and totals [4] = rows seen, rows correct, attention rows correct, rows skipped.  They accumulate over any number of
+    calls without a host synchronisation; result() performs the one copy to the host."""
+
+    def __init__(self, k, A=0, device="cuda"):
+        k, A = int(k), int(A)
+        if not 1 <= k <= MAX_CLASSES or not 0 <= A <= MAX_CLASSES:
+            raise ValueError(f"the tables take 1 <= k <= {MAX_CLASSES} classes and 0 <= A <= {MAX_CLASSES} anchors, got k = {k}, A = {A}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("the tables live on a CUDA device")
+        self.k, self.A = k, A
+        self.confusion = torch.zeros((k, k), dtype=torch.int32, device=device)
+        self.anchor_table = torch.zeros((k, A), dtype=torch.int32, device=device) if A else None
+        self.totals = torch.zeros(4, dtype=torch.int32, device=device)
+        self.attention_labelled = False
+
+    def zero_(self):
+        for t in (self.confusion, self.anchor_table, self.totals):
+            if t is not None:
+                t.zero_()
+        self.attention_labelled = False
+        return self
+
+    def result(self):
+        import numpy as np
+        confusion, totals = self.confusion.cpu().numpy(), self.totals.cpu().numpy()
+        anchor_table = None if self.anchor_table is None else self.anchor_table.cpu().numpy()
+        seen, hit, att_hit, skipped = (int(v) for v in totals)
+        per_class = confusion.sum(axis=1).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            class_acc = np.where(per_class > 0, np.diagonal(confusion) / per_class, np.nan)
+        nan = float("nan")
+        return ClassificationTally(hit / seen if seen else nan, class_acc,
+                                   att_hit / seen if seen and self.attention_labelled else nan, confusion, anchor_table, seen, skipped)
+
+
+def classification_tally(result, label, tables, attention_label=None):
+    """(result: a ClsLossResult; label int32 / int64 [B] on the device: the labels it was computed with; tables: a
+    ClassificationTables on the same device) -> tables, with every unflagged row of the batch added: confusion at (label,
+    prediction), rows seen and correct, and -- when result carries one attention row per cloud (the [B,A] layout) and the tables
+    have an anchor table -- the class x anchor table at (label, most attended anchor), upstream's commented-out lmc
+    (trainer_modelnet.py:157, :179-182); with attention_label [B] also the attention rows correct.  A row with any flag bit is
+    skipped and counted in totals[3].  One launch (epn_cls_tally_i32), nothing synchronises."""
+    if not isinstance(result, ClsLossResult):
+        raise TypeError(f"result must be a ClsLossResult, got {type(result).__name__}")
+    if not isinstance(label, torch.Tensor):
+        raise TypeError(f"label must be a torch tensor, got {type(label).__name__}")
+    if not isinstance(tables, ClassificationTables):
+        raise TypeError(f"tables must be a ClassificationTables, got {type(tables).__name__}")
+    if attention_label is not None and not isinstance(attention_label, torch.Tensor):
+        raise TypeError(f"attention_label must be a torch tensor, got {type(attention_label).__name__}")
+    B = result.preds.shape[0]
+    if tuple(label.shape) != (B,):
+        raise ValueError(f"label must be [{B}], got {tuple(label.shape)}")
+    with_att = tables.anchor_table is not None and result.att_preds is not None and result.att_preds.dim() == 1
+    if attention_label is not None:
+        if not with_att:
+            raise ValueError("attention_label needs one attention row per cloud in result and an anchor table in tables")
+        if tuple(attention_label.shape) != (B,):
+            raise ValueError(f"attention_label must be [{B}], got {tuple(attention_label.shape)}")
+    for name, t in (("label", label), ("attention_label", attention_label)):
+        if t is not None and t.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{name} must be torch.int32 or torch.int64, got {t.dtype}")
+    for name, t in (("label", label), ("attention_label", attention_label)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+    label = label.to(torch.int32).contiguous()
+    att_label = None if attention_label is None else attention_label.to(torch.int32).contiguous()
+    _lib.same_device(result.preds, label, att_label, tables.confusion)
+    p = _lib.dev_ptr
+    i32 = torch.int32
+    _lib.check(_lib.get_lib().epn_cls_tally_i32(
+        p(result.preds, "preds", i32), p(label, "label", i32), p(result.row_flags, "row_flags", i32),
+        p(result.att_preds if with_att else None, "att_preds", i32), p(att_label, "attention_label", i32),
+        p(result.att_row_flags if with_att else None, "att_row_flags", i32), B, tables.k, tables.A,
+        p(tables.confusion, "confusion", i32), p(tables.anchor_table, "anchor_table", i32), p(tables.totals, "totals", i32),
+        _lib.stream_of(label)), "classification_tally")
+    tables.attention_labelled |= att_label is not None
+    return tables
 
 
 def _check_interp(feature, T, anchors, sigma):

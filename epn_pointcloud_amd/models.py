@@ -202,6 +202,25 @@ class ClsSO3ConvModel(_SO3ConvModel):
     def forward(self, x, rlabel=None):
         return self.outblock(self.features(x), rlabel)
 
+    def classify(self, pc, *, batch=32):
+        """(pc f32 [M,N,3] on the device) -> (logits f32 [M,k], predicted class int32 [M], most attended anchor int32 [M]).  The
+        clouds go through forward() in chunks of `batch` under torch.no_grad(), in the model's current mode, which must be eval()
+        as for describe(); a short last chunk goes through as it is.  Both arg maxes are the loss kernel's
+        (losses.classification_loss: the lowest index on a tie, -1 for a row with a non-finite value); the anchor column is -1
+        for a head that pools without attention.  M = 0 returns empty tensors without a launch."""
+        from . import classification
+        if self.training:
+            raise RuntimeError("classify() needs the model in eval() mode: call model.eval() first")
+        batch = classification.check_clouds(pc, batch)
+        if pc.shape[0] > 0 and not pc.is_cuda:
+            raise RuntimeError("pc must be a CUDA tensor")
+        with torch.no_grad():
+            out = [classification.forward_chunk(self, pc[i:i + batch]) for i in range(0, pc.shape[0], batch)]
+        if not out:
+            k = self.outblock.fc2.weight.shape[0]
+            return pc.new_zeros((0, k)), pc.new_zeros((0,), dtype=torch.int32), pc.new_zeros((0,), dtype=torch.int32)
+        return tuple(torch.cat([o[i] for o in out]) for i in range(3))
+
 
 class InvSO3ConvModel(_SO3ConvModel):
     """forward(x [b, n, 3]) -> (unit descriptor [b, c_out], per-point anchor attention)."""

@@ -29,7 +29,23 @@ What differs, on purpose:
   * A device label is not range-checked on the host (torch's cross-entropy asserts on the device): an entry outside 0..A-1
     counts as zero in both terms and in the gradient, and is reported in bit 0 of `row_flags`, kept on the module with `preds`.
   * cls_loss, the L2 term and r_acc are logging values without a gradient; the angular error comes from the chordal mean's
-    Jacobi projection instead of torch.svd (3.1b)."""
+    Jacobi projection instead of torch.svd (3.1b).
+
+And of vgtk/vgtk/loss.py:CrossEntropyLoss and AttentionCrossEntropyLoss (:18-75), the losses SPConvNets/trainer_modelnet.py trains
+the classification network with, on the kernels of csrc/cls_loss.hip (losses.classification_loss).  Same
+constructors, same forward signatures, the same two and five return values, the same iter_counter (advanced in training mode
+only, the schedule weight read before it advances), NotImplementedError from forward for an unknown loss type.  What differs, on
+purpose:
+  * fp64 arithmetic inside, one rounding per output; the predicted class is the LOWEST index on a tie (torch.max leaves that
+    open).
+  * A device label is not range-checked on the host, and the device does not assert as torch's cross-entropy does: a label
+    outside the row's classes counts as zero in the loss and in the gradient and is reported in bit 0 of `row_flags` /
+    `att_row_flags`, kept on the module with `preds` / `att_preds`.  The means still divide by all rows: torch's
+    ignore_index = -100 is not special here (torch takes such rows out of the divisor).  A non-finite logit sets bit 1.
+  * acc and racc, cls_loss and r_loss are logging values without a gradient.
+  * 'no_reg' hands wts a gradient of zeros where upstream hands it None: one launch writes both gradients.
+  * The blend weights live in a two-element device buffer that the kernels read; 'schedule' rewrites it in place in every
+    call, outside any graph capture.  A captured step calls update_schedule() before each replay in forward's place."""
 import torch
 import torch.nn as nn
 
@@ -122,3 +138,104 @@ class MultiTaskDetectionLoss(nn.Module):
         if self.training:
             self.iter_counter += 1
         return r.loss, r.cls_loss, r.reg, r.r_acc, err
+
+
+class CrossEntropyLoss(nn.Module):
+    def __init__(self):
+        super(CrossEntropyLoss, self).__init__()
+        self._coef = None
+
+    def forward(self, pred, label):
+        """(pred [B,k] logits, label int [B]) -> (mean cross-entropy over dim 1, share of rows whose arg max is the label)."""
+        if self._coef is None or self._coef.device != pred.device:
+            self._coef = torch.ones(2, dtype=torch.float32, device=pred.device)      # uploaded once: the call can be captured
+        r = losses.classification_loss(pred, label.reshape(-1), coef=self._coef)
+        self.preds, self.row_flags = r.preds, r.row_flags
+        return r.loss, r.acc
+
+
+class AttentionCrossEntropyLoss(nn.Module):
+    LOSS_TYPES = ('schedule', 'default', 'no_reg')
+
+    def __init__(self, loss_type, loss_margin):
+        """loss_type 'default' (cls_loss + m r_loss), 'no_reg' (cls_loss) or 'schedule' (t cls_loss + (m + 1 - t) r_loss with
+        t = min(iter_counter / pretrain_step, 1)); anything else raises NotImplementedError in forward, as upstream;
+        loss_margin = m."""
+        super(AttentionCrossEntropyLoss, self).__init__()
+        self.loss_type = loss_type
+        self.loss_margin = loss_margin
+        self.iter_counter = 0
+        self._buffers = {}                                    # device -> float32 [2]: one buffer per device, for good
+        self._coef = None
+        self._coef_value = None
+
+    def coefficients(self, pretrain_step=2000):
+        """(c_cls, c_att) of the blend at the current iter_counter, as host floats."""
+        m = float(self.loss_margin)
+        if self.loss_type == 'schedule':
+            t = min(float(self.iter_counter) / pretrain_step, 1.0)
+            return t, m + 1.0 - t
+        if self.loss_type == 'default':
+            return 1.0, m
+        if self.loss_type == 'no_reg':
+            return 1.0, 0.0
+        raise NotImplementedError(f"{self.loss_type} is not Implemented!")
+
+    def _write_coefficients(self, device, pretrain_step):
+        value = self.coefficients(pretrain_step)
+        if device is None:
+            if self._coef is None:
+                raise RuntimeError("AttentionCrossEntropyLoss.update_schedule: name the device on the first call; no buffer exists yet")
+            device = self._coef.device
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:    # "cuda" is the current device: the same buffer as "cuda:<index>"
+            device = torch.device("cuda", torch.cuda.current_device())
+        # the buffer is allocated once per device and never replaced: a captured graph keeps reading its address
+        if self._coef is None or self._coef.device != device:
+            if device not in self._buffers:
+                self._buffers[device] = torch.empty(2, dtype=torch.float32, device=device)
+            self._coef, self._coef_value = self._buffers[device], None
+        if value != self._coef_value:                         # in place: a captured graph keeps reading this buffer
+            self._coef.copy_(torch.tensor(value, dtype=torch.float32))
+            self._coef_value = value
+        return self._coef
+
+    def update_schedule(self, device=None, pretrain_step=2000):
+        """What forward() does to the module around the loss: writes the blend weights of the current iter_counter into the
+        module's device buffer (in place; uploaded only when they changed), then advances the counter in training mode -> the
+        buffer, float32 [2].  For a captured step: forward() leaves both alone while a graph is being captured, and the trainer
+        calls this before every replay in forward's place.  device: None for the device of the buffer that exists (after the
+        first forward or call), or any spelling of a device -- "cuda" means the current device, and the buffer of a device is
+        the same tensor on every call."""
+        coef = self._write_coefficients(device, pretrain_step)
+        if self.training:
+            self.iter_counter += 1
+        return coef
+
+    def forward(self, pred, label, wts, rlabel, pretrain_step=2000):
+        """(pred [B,k], label int [B], wts [B,A] with rlabel int [B], or wts [B,C,A] with rlabel int [B,60]) ->
+        (loss, cls_loss, r_loss, acc, racc)."""
+        if self.loss_type not in self.LOSS_TYPES:
+            raise NotImplementedError(f"{self.loss_type} is not Implemented!")
+        if wts.ndimension() == 3:
+            # rlabel: B x 60 -> B x C, as upstream; wts stays [B,C,A]: upstream's transpose only moves the class axis to dim 1
+            if wts.shape[1] <= rlabel.shape[1]:
+                rlabel = rlabel[:, :wts.shape[1]]
+            else:
+                rlabel = rlabel.repeat(1, 10)[:, :wts.shape[1]]
+        else:
+            rlabel = rlabel.reshape(-1)
+        capturing = pred.is_cuda and torch.cuda.is_current_stream_capturing()
+        if capturing:
+            if self._coef is None or self._coef.device != pred.device:
+                raise RuntimeError("AttentionCrossEntropyLoss: call the loss (or update_schedule) once before capturing it: the "
+                                   "blend weights are uploaded outside the capture")
+            coef = self._coef
+        else:
+            # the weights are read BEFORE the counter advances, as upstream
+            coef = self._write_coefficients(pred.device, pretrain_step) if pred.is_cuda else self.coefficients(pretrain_step)
+        r = losses.classification_loss(pred, label.reshape(-1), wts, rlabel, coef)
+        self.preds, self.row_flags, self.att_preds, self.att_row_flags = r.preds, r.row_flags, r.att_preds, r.att_row_flags
+        if self.training and not capturing:
+            self.iter_counter += 1
+        return r.loss, r.cls_loss, r.att_loss, r.acc, r.att_acc

@@ -386,6 +386,58 @@ int epn_rotation_loss_bwd_f32(const float *upstream, const float *wts, const flo
                               const float *R_target, const int32_t *row_flags, int b, int A, int nr, double w, float *dwts,
                               float *dy, epn_stream_t stream);
 
+/* The classification network's training loss and evaluation tallies: CrossEntropyLoss and AttentionCrossEntropyLoss
+ * (vgtk/vgtk/loss.py:18-75) and the counting of the evaluation loop (SPConvNets/trainer_modelnet.py:138-210, its commented-out
+ * class x anchor table included); csrc/cls_loss.hip.  The class term and the attention term are the same
+ * problem: rows of n contiguous fp32 logits with one int32 label per row.  Class set: logits f32[B,k], label i32[B].  Attention
+ * set: att f32[R,A], att_label i32[R]; absent as a whole with R == 0 (plain CrossEntropyLoss: its pointers and A are not looked
+ * at).  For the reference's two layouts of wts: [B,A] is R = B rows; [B,C,A] is R = B C rows, row b C + c labelled rlabel[b,c].
+ * coef f32[2] = (c_cls, c_att) is DEVICE memory, read by the kernels in both directions: a captured step replays with new blend
+ * weights after an in-place update of those two floats.  All tensors are contiguous device memory.  Arithmetic is fp64 on the
+ * fp32 inputs and every output is rounded once.  No workspace, no float atomics, no host synchronisation; every float sum runs
+ * in a fixed order, so two runs are bitwise equal.
+ * Refusals, decided before any HIP runtime call: EPN_EINVAL for B outside 1..65536, k outside 1..4096, R outside 0..65536, A
+ * outside 1..4096 when R > 0, B k or R A >= 2^31 (tally: A is checked when att_pred is given); then EPN_ENULL for a required
+ * pointer that is NULL.
+ *
+ * epn_cls_loss_f32: per row x[0..n) of either set, with L its label:
+ *     row_flags bit 0: L lies outside 0..n-1 (torch asserts on the device there).  The row's row_ce is 0 and its gradient is
+ *               zero; it STAYS in the divisors B and R -- unlike torch's ignore_index = -100, which shrinks the divisor.
+ *     row_flags bit 1: an element of the row is not finite (NaN, +inf or -inf).  pred = -1; row_ce = NaN and the gradient is NaN
+ *               unless bit 0 is set as well, which wins for both.
+ *     pred      = arg max_j x[j], fp32 comparison, the LOWEST j on a tie
+ *     row_ce    = lse - x[L] with lse = m + log(sum_j exp(x[j] - m)), m the maximum; evaluated as (m - x[L]) + log(sum), whose
+ *               first term is exact, j ascending per lane (lane l adds j = l, l + 64, ...), then a fixed xor tree over the lanes
+ *   -> row_ce f32, pred i32, flags i32 per row of each set, and scalars f32[5] = (loss, cls_loss, att_loss, acc, att_acc):
+ *     cls_loss = sum row_ce / B;  att_loss = sum att_row_ce / R;  acc = #{pred == label and pred >= 0} / B, att_acc alike over R;
+ *     loss = c_cls cls_loss + c_att att_loss.  With R == 0: att_loss = att_acc = 0 and loss = c_cls cls_loss.
+ *   The sums run in fp64 over the ROUNDED per-row outputs (thread i of one workgroup adds rows i, i + 256, ... ascending, then a
+ *   fixed tree); each scalar is rounded once.  Two launches; one wave per row.
+ *
+ * epn_cls_loss_bwd_f32: upstream f32[1] (the gradient of scalars[0], on the device), the forward's inputs and its two flag arrays
+ *   -> dlogits f32[B,k], datt f32[R,A], EVERY element written.  With g = upstream:
+ *     dlogits[b,j] = g c_cls / B (softmax_j(logits[b,.]) - [j == label[b]]);  datt[r,j] = g c_att / R (softmax_j(att[r,.]) - [j == L_r])
+ *   the factor formed first, in that order, in fp64; the softmax recomputed in fp64 as above.  Rows with bit 0: zeros.  Other
+ *   rows with bit 1: NaN.  c_att == 0 writes datt as (signed) zeros; it is not skipped.  The label is range-checked again on the
+ *   device.  One launch.
+ *
+ * epn_cls_tally_i32: pred, label, flags i32[B] of the class set; optionally att_pred, att_flags i32[B] (the [B,A] layout only:
+ *   one attention row per cloud) and with them optionally att_label i32[B]; ADDS into caller-owned, caller-zeroed tables
+ *     confusion i32[k,k] at (label, pred);  anchor_table i32[k,A] at (label, att_pred) -- upstream's lmc, required with att_pred;
+ *     totals i32[4] = rows seen, rows with pred == label, rows with att_pred == att_label, rows skipped.
+ *   A row with any flag bit set in either flag array is skipped and counted in totals[3]; so is a row whose label or pred lies
+ *   outside 0..k-1 or whose att_pred lies outside 0..A-1 (nothing read from memory becomes an address unchecked).  Integer
+ *   atomics: integer addition does not depend on the order, so the tables are bitwise repeatable.  One launch. */
+int epn_cls_loss_f32(const float *logits, const int32_t *label, int B, int k, const float *att, const int32_t *att_label, int R,
+                     int A, const float *coef, float *row_ce, int32_t *pred, int32_t *flags, float *att_row_ce, int32_t *att_pred,
+                     int32_t *att_flags, float *scalars, epn_stream_t stream);
+int epn_cls_loss_bwd_f32(const float *upstream, const float *logits, const int32_t *label, const int32_t *flags, int B, int k,
+                         const float *att, const int32_t *att_label, const int32_t *att_flags, int R, int A, const float *coef,
+                         float *dlogits, float *datt, epn_stream_t stream);
+int epn_cls_tally_i32(const int32_t *pred, const int32_t *label, const int32_t *flags, const int32_t *att_pred,
+                      const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
+                      int32_t *anchor_table, int32_t *totals, epn_stream_t stream);
+
 /* The descriptor network's training loss: batch-hard triplet mining and the anchor interpolation of its equivariance term
  * (csrc/triplet_loss.hip).  All tensors are contiguous device memory, float or int32.  Arithmetic is fp64 on
  * the fp32 inputs and every output is rounded once to fp32.  No workspace, no atomics, no host synchronisation (the calls can
