@@ -8,7 +8,8 @@ Holds only what the path needs:
   matching.py  descriptor matching, the 3DMatch inlier ratio / recall and pairwise registration on the device (after models.describe)
   alignment.py  rotation decode, chordal mean and angular error on the device (after RegSO3ConvModel.forward)
   classification.py  the classification trainer's evaluation loop on the device (after ClsSO3ConvModel.forward)
-  data.py    ModelNet training batches on the device: resample, normalise, rotate, label (before the models' forward)
+  data.py    training batches on the device: ModelNet (resample, normalise, rotate, label) and 3DMatch (keypoint pairs, patches,
+             augmentation), before the models' forward
 
 `install_vgtk_alias()` registers the mirror under the reference's import names (`vgtk`,
 `vgtk.spconv`, `vgtk.so3conv`, `vgtk.cuda.grouping`, ...) so SPConvNets-style code imports unchanged.
@@ -31,7 +32,8 @@ def install_vgtk_alias():
 _MATCHING = ("match_descriptors", "evaluate_fragment_pair", "evaluate_scene", "register_scene", "register_fragment_pair",
              "registration_errors", "registration_recall", "RegistrationResult")
 _ALIGNMENT = ("decode_rotation", "evaluate_alignment")
-_DATA = ("pack_clouds", "modelnet_batch", "modelnet_alignment_batch", "ModelNetBatch")
+_DATA = ("pack_clouds", "modelnet_batch", "modelnet_alignment_batch", "ModelNetBatch", "pack_correspondences",
+         "fragment_pair_batch", "FragmentPairBatch")
 _CLASSIFICATION = ("evaluate_classification",)
 
 
@@ -39,7 +41,7 @@ def __getattr__(name):
     """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` / `.register_scene` /
     `.register_fragment_pair` / `.registration_errors` / `.registration_recall` (matching.py) and
     `.decode_rotation` / `.evaluate_alignment` (alignment.py) and `.pack_clouds` / `.modelnet_batch` /
-    `.modelnet_alignment_batch` (data.py) and `.evaluate_classification` (classification.py), resolved on first use so that importing the package -- the
+    `.modelnet_alignment_batch` / `.pack_correspondences` / `.fragment_pair_batch` (data.py) and `.evaluate_classification` (classification.py), resolved on first use so that importing the package -- the
     build recipe does -- still needs no torch."""
     if name in _MATCHING:
         from . import matching

@@ -63,7 +63,7 @@ EXPORTS = [
     "epn_ransac_register_workspace_bytes", "epn_ransac_register_f64",
     "epn_triplet_batch_hard_f32", "epn_triplet_batch_hard_bwd_f32", "epn_anchor_interp_f32", "epn_anchor_interp_bwd_f32",
     "epn_rotation_loss_f32", "epn_rotation_loss_bwd_f32",
-    "epn_modelnet_batch_f32",
+    "epn_modelnet_batch_f32", "epn_fragment_pair_batch_f32",
     "epn_cls_loss_f32", "epn_cls_loss_bwd_f32", "epn_cls_tally_i32",
 ]
 
@@ -356,6 +356,10 @@ def get_lib():
     # R_label, R_res, status)
     lib.epn_modelnet_batch_f32.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, ctypes.c_uint64, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp,
                                            _vp, _vp, _vp, _vp, _vp]
+    # 3DMatch batches: (points, m, offsets, F, pairs, B, corr, C, corr_offsets, poses, ids, n_sample, npt, radius, seed, key_bits,
+    # max_degree, center, src, tgt, idx, counts, choice, T, R_aug, T_aug, status)
+    lib.epn_fragment_pair_batch_f32.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _ci, _ci, _cf, ctypes.c_uint64,
+                                                _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     # classification loss and tallies: (logits, label, B, k, att, att_label, R, A, coef, three per-row outputs per set, scalars),
     # (upstream, logits, label, flags, B, k, att, att_label, att_flags, R, A, coef, dlogits, datt),
     # (pred, label, flags, att_pred, att_label, att_flags, B, k, A, confusion, anchor_table, totals)

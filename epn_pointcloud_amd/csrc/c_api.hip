@@ -2,6 +2,7 @@
 // Dispatch: fused MFMA kernels when cin and cout are multiples of 16, generic kernels otherwise
 // (epn_set_kernel_policy(1) forces the generic path; used by the cross-check tests).
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <cxxabi.h>
@@ -617,6 +618,26 @@ extern "C" int epn_modelnet_batch_f32(const float *points, int m, const int32_t 
     if (anchors && (!R_label || !R_res)) return EPN_EINVAL;
     return launch_modelnet_batch(points, m, offsets, b, ids, n_sample, seed, key_bits, rot_mode, R_in, anchors, A, pc_out,
                                  pc_plain, idx, R, R_label, R_res, status, epn_stream(stream));
+}
+
+// 3DMatch training batches (pair_batch.hip): sizes and scalars first, then B == 0, then pointers -- all before the first HIP
+// runtime call.  The grid is B * 2 * npt workgroups in x.
+extern "C" int epn_fragment_pair_batch_f32(const float *points, int m, const int32_t *offsets, int F, const int32_t *pairs, int B,
+                                           const float *corr, int C, const int32_t *corr_offsets, const double *poses,
+                                           const int64_t *ids, int n_sample, int npt, float radius, uint64_t seed, int key_bits,
+                                           int max_degree, int center, float *src, float *tgt, int32_t *idx, int32_t *counts,
+                                           int32_t *choice, float *T, float *R_aug, float *T_aug, int32_t *status,
+                                           epn_stream_t stream) {
+    if (B < 0 || F < 0 || m < 0 || C < 0 || n_sample < 1 || n_sample > 8192 || npt < 1 || npt > 4096) return EPN_EINVAL;
+    if (key_bits < 1 || key_bits > 32 || max_degree < 0 || max_degree > 360) return EPN_EINVAL;
+    if (!std::isfinite(radius) || !(radius > 0.0f) || (center != 0 && center != 1)) return EPN_EINVAL;
+    if ((long long)B * 2 * npt > 2147483647LL) return EPN_EINVAL;
+    if (B == 0) return 0;
+    if (!offsets || !pairs || !corr_offsets || (m > 0 && !points) || (C > 0 && !corr) || (F > 0 && !poses)) return EPN_EINVAL;
+    if (!src || !tgt || !idx || !counts || !choice || !T || !R_aug || !T_aug || !status) return EPN_EINVAL;
+    return launch_fragment_pair_batch(points, m, offsets, F, pairs, B, corr, C, corr_offsets, poses, ids, n_sample, npt, radius,
+                                      seed, key_bits, max_degree, center, src, tgt, idx, counts, choice, T, R_aug, T_aug, status,
+                                      epn_stream(stream));
 }
 
 // Classification loss and tallies (cls_loss.hip): every argument is checked before the first HIP runtime call.  Sizes first

@@ -140,6 +140,12 @@ int launch_modelnet_batch(const float *points, int m, const int32_t *offsets, in
                           uint64_t seed, int key_bits, int rot_mode, const float *R_in, const float *anchors, int A,
                           float *pc_out, float *pc_plain, int32_t *idx, float *R, int32_t *R_label, float *R_res, int32_t *status,
                           hipStream_t st);
+// pair_batch.hip: the arguments of epn_fragment_pair_batch_f32, already checked
+int launch_fragment_pair_batch(const float *points, int m, const int32_t *offsets, int F, const int32_t *pairs, int B,
+                               const float *corr, int C, const int32_t *corr_offsets, const double *poses, const int64_t *ids,
+                               int n_sample, int npt, float radius, uint64_t seed, int key_bits, int max_degree, int center,
+                               float *src, float *tgt, int32_t *idx, int32_t *counts, int32_t *choice, float *T, float *R_aug,
+                               float *T_aug, int32_t *status, hipStream_t st);
 // cls_loss.hip: the arguments of epn_cls_loss_f32, epn_cls_loss_bwd_f32 and epn_cls_tally_i32, already checked
 int launch_cls_loss(const float *logits, const int32_t *label, int B, int k, const float *att, const int32_t *att_label, int R,
                     int A, const float *coef, float *row_ce, int32_t *pred, int32_t *flags, float *att_row_ce,

@@ -6,7 +6,8 @@
 //   emit_step    one chunk of 256 consecutive indices of the ordered compaction: 64-bit ballot + popcount inside a wave, one LDS
 //                exchange (one barrier, two slot sets) across the four waves, a running base across chunks; key == T members
 //                are admitted while their rank among the ties is below `take`
-// The callers keep their own sweeps (what a member is, and what is written for a selected one, differs between them).
+// The callers keep their own sweeps (what a member is, and what is written for a selected one, differs between them); the
+// radius sweep has two callers of its own and lives in patch_sweep.h (patch_extract.hip, pair_batch.hip).
 #pragma once
 #include "epn_common.h"
 #include "philox.h"

@@ -24,126 +24,32 @@
 //   upsample   slots >= count copy slots < count of the same row back after a workgroup barrier
 // Distances and keys are recomputed in every pass (Philox only for in-radius lanes): no [k, n] workspace.  Every loop is
 // bounded by n or n_sample; no workgroup talks to another, no global atomics, no spin: the result is bitwise repeatable.
+// The sweep body itself is radius_patch_row in patch_sweep.h, shared with pair_batch.hip (3DMatch training batches).
 #include <cmath>
 
 #include "epn_common.h"
-#include "key_select.h"
+#include "patch_sweep.h"
 
 namespace {
 
-using namespace epn_keysel;        // PT, search_hist, emit_step: the selection shared with modelnet_batch.hip
-using PatchShared = Shared;
-
-__device__ __forceinline__ bool in_radius(const float *__restrict__ pc, unsigned i, float qx, float qy, float qz, float r2,
-                                          float &px, float &py, float &pz) {
-    px = pc[(size_t)3 * i]; py = pc[(size_t)3 * i + 1]; pz = pc[(size_t)3 * i + 2];
-    const float dx = __fsub_rn(px, qx), dy = __fsub_rn(py, qy), dz = __fsub_rn(pz, qz);
-    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-    return d2 <= r2;
-}
-
-__device__ __forceinline__ unsigned patch_key(unsigned i, unsigned long long Q, unsigned long long seed, int key_bits) {
-    return key_of(i, Q, seed, key_bits);
-}
+using namespace epn_keysel;        // PT, Shared, radius_patch_row: the sweep shared with pair_batch.hip (patch_sweep.h)
 
 __global__ __launch_bounds__(PT) void radius_patches_kernel(const float *__restrict__ pc, int n, const float *__restrict__ kpts,
                                                             unsigned long long kpt_row0, float radius, int n_sample,
                                                             unsigned long long seed, int key_bits, int center, float scale,
                                                             int32_t *idx, int32_t *__restrict__ counts, float *patches) {
-    __shared__ PatchShared sh;
-    const int tid = threadIdx.x;
-    const unsigned q = blockIdx.x, un = (unsigned)n;
-    const unsigned long long Q = kpt_row0 + q;
+    __shared__ Shared sh;
+    const unsigned q = blockIdx.x;
     const float qx = kpts[(size_t)3 * q], qy = kpts[(size_t)3 * q + 1], qz = kpts[(size_t)3 * q + 2];
-    const float r2 = __fmul_rn(radius, radius);
-    int32_t *irow = idx + (size_t)q * n_sample;
-    float *prow = patches + (size_t)q * n_sample * 3;
-    float px, py, pz;
-
-    // ---- pass 1: count + histogram of key bits 31..21
-    clear_hist(sh);
-    __syncthreads();
-    for (unsigned base = 0; base < un; base += PT) {
-        const unsigned i = base + tid;
-        if (i < un && in_radius(pc, i, qx, qy, qz, r2, px, py, pz))
-            atomicAdd(&sh.hist[patch_key(i, Q, seed, key_bits) >> 21], 1u);
-    }
-    unsigned b1 = 0u, b2 = 0u, b3 = 0u, take = 0u;
-    const unsigned count = search_hist(sh, (unsigned)n_sample, b1, take);
-    if (tid == 0) counts[q] = (int32_t)count;
-
-    if (count <= 1u) {
-        for (int j = tid; j < n_sample; j += PT) {
-            irow[j] = -1;
-            prow[3 * j] = 0.0f; prow[3 * j + 1] = 0.0f; prow[3 * j + 2] = 0.0f;
-        }
-        return;
-    }
-
-    // ---- passes 2, 3: the threshold key T = b1:b2:b3 and the number `take` of key == T members (count > n_sample only)
-    const bool all = count <= (unsigned)n_sample;
-    unsigned T = 0xFFFFFFFFu;
-    if (!all) {
-        clear_hist(sh);
-        __syncthreads();
-        for (unsigned base = 0; base < un; base += PT) {
-            const unsigned i = base + tid;
-            if (i < un && in_radius(pc, i, qx, qy, qz, r2, px, py, pz)) {
-                const unsigned key = patch_key(i, Q, seed, key_bits);
-                if ((key >> 21) == b1) atomicAdd(&sh.hist[(key >> 10) & 0x7FFu], 1u);
-            }
-        }
-        search_hist(sh, take, b2, take);
-        clear_hist(sh);
-        __syncthreads();
-        const unsigned hi22 = (b1 << 11) | b2;
-        for (unsigned base = 0; base < un; base += PT) {
-            const unsigned i = base + tid;
-            if (i < un && in_radius(pc, i, qx, qy, qz, r2, px, py, pz)) {
-                const unsigned key = patch_key(i, Q, seed, key_bits);
-                if ((key >> 10) == hi22) atomicAdd(&sh.hist[key & 0x3FFu], 1u);
-            }
-        }
-        search_hist(sh, take, b3, take);
-        T = (hi22 << 10) | b3;
-    }
-
-    // ---- emit: ascending index; `less` lanes always, `tie` lanes while their rank among the ties is below `take`
     const float cx = center ? qx : 0.0f, cy = center ? qy : 0.0f, cz = center ? qz : 0.0f;
-    Emit em;
-    for (unsigned base = 0; base < un; base += PT) {
-        const unsigned i = base + tid;
-        bool less = false, tie = false;
-        if (i < un && in_radius(pc, i, qx, qy, qz, r2, px, py, pz)) {
-            if (all) {
-                less = true;
-            } else {
-                const unsigned key = patch_key(i, Q, seed, key_bits);
-                less = key < T;
-                tie = key == T;
-            }
-        }
-        unsigned pos;
-        if (emit_step(sh, em, less, tie, take, pos) && pos < (unsigned)n_sample) {
-            irow[pos] = (int32_t)i;
-            prow[3 * (size_t)pos] = __fmul_rn(__fsub_rn(px, cx), scale);
-            prow[3 * (size_t)pos + 1] = __fmul_rn(__fsub_rn(py, cy), scale);
-            prow[3 * (size_t)pos + 2] = __fmul_rn(__fsub_rn(pz, cz), scale);
-        }
-    }
-
-    // ---- upsample (1 < count < n_sample): draw with replacement from the row's first `count` slots
-    if (count < (unsigned)n_sample) {
-        __threadfence_block();
-        __syncthreads();                               // the row's first `count` slots are written and visible to the workgroup
-        for (unsigned j = count + tid; j < (unsigned)n_sample; j += PT) {
-            const unsigned src = epn::philox::philox4x32_10((unsigned long long)j, Q, seed).w[1] % count;
-            irow[j] = irow[src];
-            prow[3 * (size_t)j] = prow[3 * (size_t)src];
-            prow[3 * (size_t)j + 1] = prow[3 * (size_t)src + 1];
-            prow[3 * (size_t)j + 2] = prow[3 * (size_t)src + 2];
-        }
-    }
+    const unsigned count = radius_patch_row(
+        sh, pc, (unsigned)n, qx, qy, qz, radius, n_sample, kpt_row0 + q, seed, key_bits, idx + (size_t)q * n_sample,
+        patches + (size_t)q * n_sample * 3, [=](float px, float py, float pz, float *out) {
+            out[0] = __fmul_rn(__fsub_rn(px, cx), scale);
+            out[1] = __fmul_rn(__fsub_rn(py, cy), scale);
+            out[2] = __fmul_rn(__fsub_rn(pz, cz), scale);
+        });
+    if (threadIdx.x == 0) counts[q] = (int32_t)count;
 }
 
 }  // namespace

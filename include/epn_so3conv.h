@@ -175,6 +175,61 @@ int epn_modelnet_batch_f32(const float *points, int m, const int32_t *offsets, i
                            float *pc_out, float *pc_plain, int32_t *idx, float *R, int32_t *R_label, float *R_res,
                            int32_t *status, epn_stream_t stream);
 
+/* 3DMatch training batches: a batch of fragment pairs with their keypoint correspondences -> the two patch tensors the
+ * descriptor network trains on, the pair's relative rotation and the augmentation that was applied.  Replaces the host path of
+ * the reference's FragmentLoader.__getitem__ (SPConvNets/datasets/match_3dmatch.py:301-354), which per pair, in a DataLoader
+ * worker, draws npt correspondences with replacement (np.random.choice), cuts a radius patch around each keypoint in both
+ * fragments (scipy KDTree), resamples every patch to input_num points (pctk.uniform_resample_np, vgtk/vgtk/pc/sample.py:16-36),
+ * draws one Euler rotation per side (pctk.rotate_point_cloud(None, max_degree=30), vgtk/vgtk/pc/augmentation.py:16-33 and
+ * :58-89), rotates the patches and returns T = R_A^T R_B.  Those draws cannot be reproduced; this is the library's own
+ * deterministic form of the same semantics (csrc/pair_batch.hip).
+ *   points f32[m,3], offsets i32[F+1] ON THE DEVICE: the F downsampled fragments of the batch, concatenated; fragment f is rows
+ *   offsets[f] .. offsets[f+1]-1: the search support.  pairs i32[B,2]: the source and the target fragment of each sample, as rows
+ *   of offsets; a fragment may serve several samples, source == target is allowed.  corr f32[C,2,3], corr_offsets i32[B+1]:
+ *   sample b's keypoint correspondences are rows corr_offsets[b] .. corr_offsets[b+1]-1, P_b of them; entry [.,0] is a coordinate
+ *   in the source fragment's frame and [.,1] in the target's (the reference takes them from the raw fragments).  poses f64[F,4,4]
+ *   (row-major).  ids i64[B] on the device or NULL (id_b = b): the sample's identity, 0 <= id < 2^40, e.g. dataset index + epoch
+ *   * dataset length.
+ *   -> src, tgt f32[B,npt,n_sample,3], idx i32[B,2,npt,n_sample] (rows within the fragment), counts i32[B,2,npt],
+ *      choice i32[B,npt], T f32[B,3,3], R_aug f32[B,2,3,3], T_aug f32[B,3,3], status i32[B]; every element is written on every call.
+ * Every draw depends on (seed, id, npt) only -- never on b, on B or on the other samples.  The patch of sample id, side s
+ * (0 source, 1 target), slot j has the stream Q' = (id * 2 + s) * npt + j.
+ *   choice        choice[b,j] = word0(Philox4x32-10(ctr_lo = 2^32, ctr_hi = Q'(0,j), key = seed)) mod P_b: a draw with
+ *                 replacement, at a counter no point index reaches; both sides use the same correspondence.
+ *   patch         exactly the rule of epn_radius_patches_f32 applied to the rows of the side's fragment, with the keypoint
+ *                 corr[choice[b,j], s] and the global row Q': the individually rounded fp32 distance, the inclusive comparison,
+ *                 the (key, i) selection written in ascending i, the upsample draw and the count <= 1 zero row.  idx[b,s,j] and
+ *                 counts[b,s,j] are bit for bit what that entry returns for the fragment alone with kpt_row0 = Q'.
+ *   augmentation  side s: w = Philox4x32-10(ctr_lo = 2^32 + 1, ctr_hi = Q'(s,0), key = seed); degrees d_k = w[k] mod max_degree,
+ *                 k = 0, 1, 2: integers in [0, max_degree) like np.random.randint(0, max_degree, 3), with a modulo bias of about
+ *                 max_degree / 2^32; angles (d_k * pi) / 180; R = Rz(d_2) Ry(d_1) Rx(d_0) (R_from_euler_np) in fp64, rounded
+ *                 once to fp32: that fp32 matrix is R_aug[b,s].  max_degree = 0: R = I (the reference's no_augmentation).
+ *   values        R (p - center * q), center 0 or 1: the subtraction rounded in fp32 as in epn_radius_patches_f32, then each
+ *                 component ((r0 x + r1 y) + r2 z) in fp64 from the ROUNDED R, rounded once: the returned R_aug is exactly the
+ *                 rotation that was applied.  Zero rows stay zero.
+ *   transforms    T = R_A^T R_B from the upper-left 3 x 3 blocks of poses[pairs[b,0]] and poses[pairs[b,1]], each entry
+ *                 ((a0 b0 + a1 b1) + a2 b2) in fp64, rounded once (what the reference returns).  T_aug = (R_aug_src T) R_aug_tgt^T
+ *                 from the three rounded matrices in fp64, rounded once: the relation the augmented patches satisfy (the reference
+ *                 returns T although it hands rotated patches to the loss).
+ *   status        a sample carries the first that applies: 8 a pairs entry outside [0,F), or offsets of one of its fragments or
+ *                 its corr_offsets descending or outside [0,m] / [0,C]; 1 no correspondences; 4 a non-finite entry in one of its
+ *                 two poses (all 16) or a non-finite coordinate in one of its npt chosen correspondences (either side); 0
+ *                 otherwise.  A sample with a status reads nothing out of range; its src, tgt, T and T_aug are zeros, its idx and
+ *                 choice -1, its counts 0; its R_aug is still drawn.  Nothing asserts; no sample affects another.  An empty patch
+ *                 (also an empty fragment) is reported through counts, not through status.
+ * Refusals, decided before any HIP runtime call, all EPN_EINVAL: B, F, m or C negative, n_sample outside 1..8192, npt outside
+ * 1..4096, key_bits outside 1..32, max_degree outside 0..360, radius not finite or not > 0, center not 0 or 1, B * 2 * npt
+ * beyond 2^31 - 1; then B == 0 succeeds and launches nothing; then a required pointer that is NULL (everything but ids; points
+ * only when m > 0, corr only when C > 0, poses only when F > 0).  One launch of B * 2 * npt workgroups of 256 threads, each
+ * doing what a workgroup of epn_radius_patches_f32 does and recomputing its sample's status and its side's R itself; no
+ * workspace, no global atomics, no allocation, no host synchronisation (the call can be captured into a HIP graph and replayed
+ * after ids were rewritten in place): two calls are bitwise equal. */
+int epn_fragment_pair_batch_f32(const float *points, int m, const int32_t *offsets, int F, const int32_t *pairs, int B,
+                                const float *corr, int C, const int32_t *corr_offsets, const double *poses, const int64_t *ids,
+                                int n_sample, int npt, float radius, uint64_t seed, int key_bits, int max_degree, int center,
+                                float *src, float *tgt, int32_t *idx, int32_t *counts, int32_t *choice, float *T, float *R_aug,
+                                float *T_aug, int32_t *status, epn_stream_t stream);
+
 /* Descriptor matching: for every fragment pair of a scene, the exact nearest neighbour in descriptor space in both
  * directions, then the mutual check "tgt -> src -> tgt", the ground-truth transform and the inlier count.  Replaces the host
  * block of the reference's evaluation (SPConvNets/datasets/evaluation_3dmatch.py:77-100: two sklearn KDTrees, the mutual
