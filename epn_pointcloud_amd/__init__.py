@@ -8,6 +8,7 @@ Holds only what the path needs:
   matching.py  descriptor matching, the 3DMatch inlier ratio / recall and pairwise registration on the device (after models.describe)
   alignment.py  rotation decode, chordal mean and angular error on the device (after RegSO3ConvModel.forward)
   classification.py  the classification trainer's evaluation loop on the device (after ClsSO3ConvModel.forward)
+  optim.py   the trainers' optimiser on the device: Adam over all parameters in two launches (after backward)
   data.py    training batches on the device: ModelNet (resample, normalise, rotate, label) and 3DMatch (keypoint pairs, patches,
              augmentation), before the models' forward
 
@@ -35,13 +36,14 @@ _ALIGNMENT = ("decode_rotation", "evaluate_alignment")
 _DATA = ("pack_clouds", "modelnet_batch", "modelnet_alignment_batch", "ModelNetBatch", "pack_correspondences",
          "fragment_pair_batch", "FragmentPairBatch")
 _CLASSIFICATION = ("evaluate_classification",)
+_OPTIM = ("FlatAdam",)
 
 
 def __getattr__(name):
     """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` / `.register_scene` /
     `.register_fragment_pair` / `.registration_errors` / `.registration_recall` (matching.py) and
     `.decode_rotation` / `.evaluate_alignment` (alignment.py) and `.pack_clouds` / `.modelnet_batch` /
-    `.modelnet_alignment_batch` / `.pack_correspondences` / `.fragment_pair_batch` (data.py) and `.evaluate_classification` (classification.py), resolved on first use so that importing the package -- the
+    `.modelnet_alignment_batch` / `.pack_correspondences` / `.fragment_pair_batch` (data.py) and `.evaluate_classification` (classification.py) and `.FlatAdam` (optim.py), resolved on first use so that importing the package -- the
     build recipe does -- still needs no torch."""
     if name in _MATCHING:
         from . import matching
@@ -55,4 +57,7 @@ def __getattr__(name):
     if name in _CLASSIFICATION:
         from . import classification
         return getattr(classification, name)
+    if name in _OPTIM:
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

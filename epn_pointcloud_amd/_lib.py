@@ -65,6 +65,7 @@ EXPORTS = [
     "epn_rotation_loss_f32", "epn_rotation_loss_bwd_f32",
     "epn_modelnet_batch_f32", "epn_fragment_pair_batch_f32",
     "epn_cls_loss_f32", "epn_cls_loss_bwd_f32", "epn_cls_tally_i32",
+    "epn_adam_workspace_bytes", "epn_adam_check_plan", "epn_adam_step_f32",
 ]
 
 _vp, _ci, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -367,6 +368,14 @@ def get_lib():
     lib.epn_cls_loss_bwd_f32.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]
     lib.epn_cls_tally_i32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]
     lib.epn_cls_tally_i32.restype = _ci
+    # Adam step: (n), (host seg_param, host seg_off, nseg, n), (seg_param, seg_off, nseg, n, grad, exp_avg, exp_avg_sq, lr, beta1,
+    # beta2, eps, weight_decay, grad_scale, max_norm, counters, info, workspace, workspace_bytes, stream)
+    _cd, _ll = ctypes.c_double, ctypes.c_longlong
+    lib.epn_adam_workspace_bytes.argtypes = [_ll]
+    lib.epn_adam_workspace_bytes.restype = _sz
+    lib.epn_adam_check_plan.argtypes = [_vp, _vp, _ci, _ll]
+    lib.epn_adam_check_plan.restype = _ci
+    lib.epn_adam_step_f32.argtypes = [_vp, _vp, _ci, _ll, _vp, _vp, _vp, _vp, _cd, _cd, _cd, _cd, _cd, _cd, _vp, _vp, _vp, _sz, _vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
         if name.endswith("_f32") or name.endswith("_bf16") or name in ("epn_transpose_cast", "epn_cast"):
@@ -379,7 +388,8 @@ def get_lib():
 # Host-only entry points (no stream argument, nothing launched): handed out unwrapped.
 _HOST_ONLY = {"epn_inter_bwd_data_f16x2_ok", "epn_inter_ungroup_cloud_ok", "epn_inter_ungroup_cloud_range_count", "epn_version", "epn_strerror", "epn_set_kernel_policy", "epn_last_kernel", "epn_f16x2_overflow_count", "epn_inter_is_fused", "epn_inter_split_ok", "epn_inter_c1_ok",
               "epn_inter_split_saved_bytes",
-              "epn_intra_is_fused", "epn_inter_onchip_ok", "epn_inter_group_packed_ok", "epn_inter_packed_position"}
+              "epn_intra_is_fused", "epn_inter_onchip_ok", "epn_inter_group_packed_ok", "epn_inter_packed_position",
+              "epn_adam_check_plan"}
 CALL_HOOK = None      # ops.profile_begin(): callable(name, fn, args) -> rc, brackets every launching call with HIP events
 
 

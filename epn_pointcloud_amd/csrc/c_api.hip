@@ -675,3 +675,33 @@ extern "C" int epn_cls_tally_i32(const int32_t *pred, const int32_t *label, cons
     return launch_cls_tally(pred, label, flags, att_pred, att_pred ? att_label : nullptr, att_flags, B, k, A, confusion,
                             anchor_table, totals, epn_stream(stream));
 }
+
+// Adam step (adam_step.hip): every refusal is decided before the first HIP runtime call.  Sizes and hyper-parameters first
+// (EPN_EINVAL; the comparisons are written so that a NaN fails them), then pointers (EPN_ENULL), then the workspace
+static bool adam_sizes_ok(int nseg, long long n) { return nseg >= 1 && nseg <= 65536 && n >= 1 && n < (1LL << 40) && nseg <= n; }
+
+extern "C" size_t epn_adam_workspace_bytes(long long n) { return adam_workspace_bytes(n); }
+
+extern "C" int epn_adam_check_plan(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n) {
+    if (!(nseg >= 1 && nseg <= 65536 && n >= 1 && n < (1LL << 40))) return EPN_EINVAL;
+    if (!seg_param || !seg_off) return EPN_ENULL;
+    if (seg_off[0] != 0 || seg_off[nseg] != n) return EPN_EINVAL;
+    for (int s = 0; s < nseg; ++s)
+        if (seg_off[s + 1] <= seg_off[s] || seg_param[s] == 0 || (seg_param[s] & 3) != 0) return EPN_EINVAL;
+    return 0;
+}
+
+extern "C" int epn_adam_step_f32(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n,
+                                 const float *grad, float *exp_avg, float *exp_avg_sq, const float *lr, double beta1,
+                                 double beta2, double eps, double weight_decay, double grad_scale, double max_norm,
+                                 int32_t *counters, float *info, void *workspace, size_t workspace_bytes, epn_stream_t stream) {
+    if (!adam_sizes_ok(nseg, n)) return EPN_EINVAL;
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return EPN_EINVAL;
+    if (!(eps > 0.0 && eps < INFINITY) || !(weight_decay >= 0.0 && weight_decay < INFINITY)) return EPN_EINVAL;
+    if (!(grad_scale >= 0.0 && grad_scale < INFINITY) || max_norm != max_norm) return EPN_EINVAL;
+    if (!seg_param || !seg_off || !grad || !exp_avg || !exp_avg_sq || !lr || !counters || !info) return EPN_ENULL;
+    if (!workspace || workspace_bytes < adam_workspace_bytes(n) || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)
+        return EPN_EWORKSPACE;
+    return launch_adam_step(seg_param, seg_off, nseg, n, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
+                            grad_scale, max_norm, counters, info, workspace, epn_stream(stream));
+}

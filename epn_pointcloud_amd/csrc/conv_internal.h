@@ -157,4 +157,11 @@ int launch_cls_tally(const int32_t *pred, const int32_t *label, const int32_t *f
                      const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
                      int32_t *anchor_table, int32_t *totals, hipStream_t st);
 
+// adam_step.hip: the arguments of epn_adam_step_f32, already checked; the bytes epn_adam_workspace_bytes reports
+size_t adam_workspace_bytes(long long n);
+int launch_adam_step(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n, const float *grad,
+                     float *exp_avg, float *exp_avg_sq, const float *lr, double beta1, double beta2, double eps,
+                     double weight_decay, double grad_scale, double max_norm, int32_t *counters, float *info, void *workspace,
+                     hipStream_t st);
+
 }  // namespace epn

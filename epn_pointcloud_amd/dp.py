@@ -249,10 +249,12 @@ class GradBuckets:
     def _span_all(self):
         return [(self.spans[0][0], self.spans[-1][1])]
 
-    def finish(self, one_collective=False):
+    def finish(self, one_collective=False, average=True):
         """Complete this step's all-reduces (issuing them first when no hooks ran) and average.  one_collective=True (no
         hooks: nothing to overlap with) sends the whole flat buffer as ONE all-reduce -- xGMI is point-to-point, a ring
-        step costs its latency per collective.  Returns the number of collectives of the step."""
+        step costs its latency per collective.  average=False leaves the SUM in the buffer, for an optimiser that folds the
+        1/world in (optim.FlatAdam(world=world)) and spares the pass over the buffer.  Returns the number of collectives of
+        the step."""
         if self.world <= 1 and not self.force:
             return 0
         rec = None
@@ -291,7 +293,7 @@ class GradBuckets:
             else:
                 import time
                 self.timings.append((time.perf_counter() - rec) * 1e3)
-        if self.world > 1 or self.force:
+        if average and (self.world > 1 or self.force):
             self.flat.div_(self.world)
         self._pending = [len(b) for b in self.buckets]
         return n

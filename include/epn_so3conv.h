@@ -493,6 +493,55 @@ int epn_cls_tally_i32(const int32_t *pred, const int32_t *label, const int32_t *
                       const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
                       int32_t *anchor_table, int32_t *totals, epn_stream_t stream);
 
+/* Adam over every parameter of a model in one call: the optimiser of the three trainers (optim.Adam driven by
+ * vgtk.LearningRateScheduler, vgtk/vgtk/app/trainer.py:162-168); csrc/adam_step.hip.  Two launches, no host
+ * synchronisation, no allocation, no float atomics; capturable on one stream; two runs from equal state are bitwise equal.
+ * amsgrad is not built.
+ * Operands, all contiguous fp32 device memory: nseg parameter segments, reached through seg_param u64[nseg] (their device
+ * addresses, each 4-byte aligned; the parameters stay where they are) and seg_off i64[nseg + 1] (seg_off[0] = 0, strictly
+ * increasing, seg_off[nseg] = n: segment s is the flat range seg_off[s] .. seg_off[s + 1] - 1), both tables in DEVICE memory;
+ * three flat buffers of n elements that share those offsets: grad (read only), exp_avg, exp_avg_sq.  A segment may start at any
+ * 4-byte boundary; 16-byte accesses are used where the flat buffers and the parameter's address allow them, per four elements.
+ * lr f32[1] is DEVICE memory, read by the kernel: a captured step replays with a new rate after an in-place write of that float.
+ * counters i32[2] = (steps_applied, steps_skipped), caller-zeroed at the start of training; info f32[4] is written by every call.
+ *
+ * The flat index space is cut into chunks of EPN_ADAM_SPAN elements, contiguous runs of chunks per workgroup, the partition
+ * fixed by n alone.  With s = grad_scale:
+ *   pass A  sumsq = sum (s g)^2 in fp64 (per thread ascending, a fixed tree per workgroup, one partial per workgroup into the
+ *           workspace) and the number of non-finite elements of g; steps_applied is copied into the workspace.
+ *   pass B  every workgroup adds the partials in one fixed order (the same bits in all of them) and forms
+ *             norm = sqrt(sumsq);  skip = (nonfinite > 0) or not finite(norm);
+ *             c = 1 when max_norm <= 0 or max_norm = +inf, else max_norm / (norm + 1e-6) where that is < 1, else 1 (a NaN
+ *             quotient gives 1): the rule of torch's clip_grad_norm_.
+ *           info = (norm, c, lr as read, skip as 0 or 1), each rounded once.  With skip set, steps_skipped grows by one and
+ *           NOTHING else is written: p, exp_avg, exp_avg_sq and steps_applied keep their bits.  Otherwise steps_applied becomes
+ *           t = steps_applied + 1 (written by one workgroup; all read the copy pass A made, so none sees the new value), and per
+ *           element, in fp64 on the fp32 inputs, no fused multiply-add, every stored value rounded once to nearest with
+ *           subnormals kept:
+ *             g' = (s c) g + weight_decay p
+ *             m' = fl32(beta1 m + (1 - beta1) g')
+ *             v' = fl32(beta2 v + (1 - beta2) (g' g'))
+ *             p' = fl32(p - ((lr / (1 - beta1^t)) m') / (sqrt(v') / sqrt(1 - beta2^t) + eps))
+ *           p' is formed from the ROUNDED m' and v': the stored state determines the next step, as in torch.optim.Adam.
+ * A finite gradient cannot overflow sumsq: n < 2^40 squares below 2^256 stay below 2^296.
+ *
+ * epn_adam_workspace_bytes(n): host only; positive, never decreasing in n.  The workspace needs 8-byte alignment.
+ * epn_adam_check_plan: host only, on HOST copies of the two tables.  EPN_EINVAL unless 1 <= nseg <= 65536, seg_off[0] == 0, the
+ *   offsets increase strictly, seg_off[nseg] == n, 1 <= n < 2^40 and every address is non-zero and 4-byte aligned (EPN_ENULL
+ *   for a NULL table).
+ * epn_adam_step_f32 refusals, decided before any HIP runtime call: EPN_EINVAL for nseg outside 1..65536, n outside 1..2^40 - 1,
+ *   nseg > n, beta1 or beta2 outside [0, 1), eps <= 0, a negative or non-finite eps, weight_decay or grad_scale (NaN included),
+ *   a NaN max_norm; then EPN_ENULL for seg_param, seg_off, grad, exp_avg, exp_avg_sq, lr, counters or info NULL; then
+ *   EPN_EWORKSPACE for a workspace that is NULL, misaligned or smaller than epn_adam_workspace_bytes(n).  The device tables are
+ *   not read on the host: validate them with epn_adam_check_plan when they are built. */
+#define EPN_ADAM_SPAN 1024
+size_t epn_adam_workspace_bytes(long long n);
+int epn_adam_check_plan(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n);
+int epn_adam_step_f32(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n, const float *grad,
+                      float *exp_avg, float *exp_avg_sq, const float *lr, double beta1, double beta2, double eps,
+                      double weight_decay, double grad_scale, double max_norm, int32_t *counters, float *info, void *workspace,
+                      size_t workspace_bytes, epn_stream_t stream);
+
 /* The descriptor network's training loss: batch-hard triplet mining and the anchor interpolation of its equivariance term
  * (csrc/triplet_loss.hip).  All tensors are contiguous device memory, float or int32.  Arithmetic is fp64 on
  * the fp32 inputs and every output is rounded once to fp32.  No workspace, no atomics, no host synchronisation (the calls can
