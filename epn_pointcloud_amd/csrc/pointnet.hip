@@ -220,7 +220,12 @@ __global__ __launch_bounds__(256) void pointnet_fwd_mfma_kernel(PnArgs A) {
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     const float v = acc[mt][nt][r] + bias[nt] + w3[nt][0] * e0 + w3[nt][1] * e1 + w3[nt][2] * e2;
-                    if (p0 + pl < A.p && pn_takes(v, best[nt])) { best[nt] = v; bestp[nt] = p0 + pl; }   // ascending p: first max
+                    // ascending p: first max.  Two selects on one flag, not a branch: as `if (...) { best = v; bestp = ... }` the
+                    // compiler dropped pn_takes' NaN clause from the first step (mt = r = nt = 0), and a NaN at a point
+                    // 4 j of a 64-point tile never reached the first 16 channels of a wave (CHANGELOG)
+                    const bool take = p0 + pl < A.p && pn_takes(v, best[nt]);
+                    best[nt] = take ? v : best[nt];
+                    bestp[nt] = take ? p0 + pl : bestp[nt];
                 }
             }
     }
