@@ -59,6 +59,7 @@ EXPORTS = [
     "epn_radius_patches_f32",
     "epn_nn_match_workspace_bytes", "epn_nn_match_f32", "epn_match_inliers_f64",
     "epn_voxel_downsample_workspace_bytes", "epn_voxel_downsample_f32",
+    "epn_point_grid_workspace_bytes", "epn_point_grid_build_f32", "epn_point_grid_nn_f32",
     "epn_rotation_labels_f32", "epn_so3_mean_f32", "epn_rotation_decode_f32",
     "epn_ransac_register_workspace_bytes", "epn_ransac_register_f64",
     "epn_triplet_batch_hard_f32", "epn_triplet_batch_hard_bwd_f32", "epn_anchor_interp_f32", "epn_anchor_interp_bwd_f32",
@@ -329,6 +330,12 @@ def get_lib():
     lib.epn_voxel_downsample_workspace_bytes.argtypes = [ctypes.c_int64]
     lib.epn_voxel_downsample_workspace_bytes.restype = _sz
     lib.epn_voxel_downsample_f32.argtypes = [_vp, ctypes.c_int64, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+    # point grid: (ref, n, ref_valid, max_radius, workspace, bytes, status, stream),
+    # (workspace, n, qry, m, radius, exclude_row, nn_idx, nn_d2, hits, stream)
+    lib.epn_point_grid_workspace_bytes.argtypes = [ctypes.c_int64]
+    lib.epn_point_grid_workspace_bytes.restype = _sz
+    lib.epn_point_grid_build_f32.argtypes = [_vp, ctypes.c_int64, _vp, ctypes.c_double, _vp, _sz, _vp, _vp]
+    lib.epn_point_grid_nn_f32.argtypes = [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_double, _ci, _vp, _vp, _vp, _vp]
     # rotation estimation: (anchors, T, b, A, ...), (Rs, weights, b, N, ...), (wts, y, anchors, label, gt_T, b, A, nr, ...)
     lib.epn_rotation_labels_f32.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp, _vp]
     lib.epn_so3_mean_f32.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp, _vp]

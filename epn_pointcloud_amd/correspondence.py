@@ -1,0 +1,167 @@
+"""Keypoint correspondences of 3DMatch fragment pairs on the device: what the reference computes on the host, once per dataset,
+with sklearn trees and open3d (SPConvNets/datasets/preprocess/run_keypoint.py) and stores as the cloud_bin_i-cloud_bin_j.npy
+files its training loader reads (SPConvNets/datasets/match_3dmatch.py:233-304).  Every step is one primitive, the nearest point
+of a cloud within a bound, served by a hashed grid (csrc/point_grid.hip; include/epn_so3conv.h: epn_point_grid_build_f32,
+epn_point_grid_nn_f32):
+
+  fragment_overlap      test_scenes_overlap (:98-112): how many source points have a target point within the margin
+  keypoint_pairs        generate_kp (:114-141): downsample both fragments, drop isolated centroids, match the rest across the
+                        fragments, map every matched centroid back to a raw row
+  scene_keypoint_pairs  run_KeypointSelection's pair schedule (:162-185) over the fragments of one scene
+
+The clouds are in the WORLD frame (transform_points applies a pose); inputs are device tensors, and a host tensor raises like
+every other wrapper of the library (no CPU fallback).  The FPFH descriptor is not computed: the reference calls
+cross_filtering_via_fpfh with nonplanar_param = -1, so all it uses of the descriptor is whether it is zero (:58-59), and in
+open3d's algorithm a point's descriptor is zero exactly when no other point of its cloud lies within the FPFH radius -- the
+isolation filter below.  That equivalence is argued from open3d's algorithm; it has not been run against open3d."""
+import collections
+import math
+
+import torch
+
+from . import _lib
+from .data import _tensor
+
+KeypointPairs = collections.namedtuple("KeypointPairs", ["rows", "src_centroid_row", "d2"])
+
+
+def _grouping():
+    """vgtk.cuda.grouping, on first use: vgtk.pc re-exports this module's functions, so neither imports the other at import
+    time."""
+    from .vgtk.cuda import grouping
+    return grouping
+
+
+def transform_points(pc, T):
+    """(pc f[n,3], T [4,4]) -> f32 [n,3]: R p + t, computed in fp64 and rounded once (the reference transforms with open3d, in
+    fp64, before it searches: run_keypoint.py:118, :166)."""
+    T = torch.as_tensor(T, dtype=torch.float64, device=pc.device)
+    if T.shape != (4, 4):
+        raise ValueError(f"T must be [4,4], got {tuple(T.shape)}")
+    return (pc.to(torch.float64) @ T[:3, :3].T + T[:3, 3]).to(torch.float32)
+
+
+class PointGrid:
+    """The grid of one cloud: PointGrid(points f32 [n,3], max_radius, valid=None) builds it (seven launches) and owns its
+    workspace; .nearest() answers any radius up to max_radius.  Points with a non-finite coordinate, and those whose `valid`
+    byte is zero, are never an answer.  The status word is read back once; a range error raises ValueError naming its bit, as
+    vgtk.pc.voxel_down_sample does."""
+
+    def __init__(self, points, max_radius, valid=None):
+        self.points = _tensor(points, "points", (None, 3), torch.float32)
+        self.n = self.points.shape[0]
+        self.max_radius = float(max_radius)
+        grouping = _grouping()
+        self._workspace, status = grouping.point_grid_build(self.points, self.max_radius, valid)
+        self.kept = 0
+        if status is not None:
+            self.kept, flags = status.tolist()
+            if flags:
+                raise ValueError("PointGrid: status " + "; ".join(t for b, t in enumerate(grouping._VOXEL_FLAGS) if flags >> b & 1)
+                                 + f" (flags = {flags}, max_radius = {self.max_radius})")
+
+    def nearest(self, queries, radius, exclude_self=False, count=False):
+        """queries f32 [m,3] -> (idx int32 [m], d2 f32 [m][, hits int32 [1]]): the row of the nearest point within radius (the
+        smallest fp32 squared distance, the lowest row on a tie) and that distance, -1 and +inf without one.  exclude_self: the
+        queries are the grid's own points, and each skips its own row (a duplicate at another row is still found).  count: also
+        the number of queries that found a point, on the device."""
+        if not float(radius) <= self.max_radius:
+            raise ValueError(f"radius must not exceed the grid's max_radius {self.max_radius}, got {radius}")
+        return _grouping().point_grid_nn(self._workspace, self.n, queries, radius, exclude_row=exclude_self, count=count)
+
+
+def _grid(cloud, name, max_radius):
+    """cloud: a PointGrid (its max_radius must cover max_radius) or a tensor to build one from."""
+    if isinstance(cloud, PointGrid):
+        if cloud.max_radius < max_radius:
+            raise ValueError(f"{name}: the grid was built for radii up to {cloud.max_radius}, {max_radius} is needed")
+        return cloud
+    return PointGrid(_tensor(cloud, name, (None, 3), torch.float32), max_radius)
+
+
+def fragment_overlap(src, tgt, margin=0.075, ratio=0.3):
+    """(src f32 [n_src,3], tgt f32 [n_tgt,3] or its PointGrid, both in the world frame) -> (hits int32 [], overlaps bool [], on
+    the device): hits = the number of source points with a target point within margin; overlaps = hits >= ratio *
+    max(n_src, n_tgt), the reference's test_scenes_overlap (run_keypoint.py:98-112; the product in fp64 as there).  The
+    reference subsamples both clouds to subsample_maxpoints first; that is the caller's here (rows drawn with torch.randint)."""
+    src = _tensor(src, "src", (None, 3), torch.float32)
+    grid = _grid(tgt, "tgt", float(margin))
+    hits = grid.nearest(src, margin, count=True)[2][0]
+    need = math.ceil(float(ratio) * max(src.shape[0], grid.n))      # an integer count reaches the product iff it reaches its ceiling
+    return hits, hits >= need
+
+
+def raw_radius(voxel_size):
+    """voxel_size * sqrt(3), the voxel's diagonal: a centroid lies inside its voxel, which holds a raw point."""
+    return float(voxel_size) * math.sqrt(3.0)
+
+
+def keypoint_pairs(src_world, tgt_world, *, voxel_size=0.05, isolation_radius=0.15, match_radius=0.03):
+    """(src_world, tgt_world: f32 [n,3] in the world frame, or the PointGrid of one, built with max_radius >=
+    raw_radius(voxel_size)) -> KeypointPairs(rows int32 [P,2], src_centroid_row int32 [P], d2 f32 [P]): the reference's
+    generate_kp (run_keypoint.py:125-141) for one pair.  In this order:
+      1. vgtk.pc.voxel_down_sample of both clouds at voxel_size;
+      2. a centroid is kept when another centroid of its cloud lies within isolation_radius (the zero-FPFH filter, :58-59);
+      3. every kept source centroid takes the nearest kept target centroid within match_radius (:66-67), or drops out;
+      4. each surviving centroid is replaced by the row of the nearest raw point of its fragment (:131-138), searched within
+         raw_radius(voxel_size); a centroid without one is a bug and raises RuntimeError.
+    rows[:,0] are rows of the source cloud and rows[:,1] of the target cloud, in ascending source-centroid row; d2 is the squared
+    centroid distance of step 3.  The survivors are compacted with a torch mask, and the status words of the two downsamplings and
+    of the grids built here are read back: a handful of host synchronisations per pair of fragments, none per point."""
+    from .vgtk.pc import voxel_down_sample
+    R = raw_radius(voxel_size)
+    raw = [_grid(src_world, "src_world", R), _grid(tgt_world, "tgt_world", R)]
+    cen = [voxel_down_sample(g.points, voxel_size)[0] for g in raw]
+    keep = [PointGrid(c, isolation_radius).nearest(c, isolation_radius, exclude_self=True)[0] >= 0 for c in cen]
+    idx, d2 = PointGrid(cen[1], match_radius, valid=keep[1]).nearest(cen[0], match_radius)
+    sel = torch.nonzero(keep[0] & (idx >= 0)).reshape(-1)           # ascending; the one compaction
+    partner = idx[sel].to(torch.int64)
+    rows = torch.stack((raw[0].nearest(cen[0][sel], R)[0], raw[1].nearest(cen[1][partner], R)[0]), dim=1)
+    if sel.numel() and int(rows.min()) < 0:
+        raise RuntimeError("keypoint_pairs: a voxel centroid has no raw point within its voxel's diagonal")
+    return KeypointPairs(rows, sel.to(torch.int32), d2[sel])
+
+
+def pair_schedule(n_fragments, stride=4, window=20):
+    """[(i, j)]: for every fragment i, j in range(i + 1, min(i + window, n), stride) (run_keypoint.py:162, :175)."""
+    return [(i, j) for i in range(n_fragments) for j in range(i + 1, min(i + window, n_fragments), stride)]
+
+
+def scene_keypoint_pairs(clouds_world, clouds_local=None, *, stride=4, window=20, margin=0.075, ratio=0.3, voxel_size=0.05,
+                         isolation_radius=0.15, match_radius=0.03):
+    """(clouds_world: the F fragments of a scene in the world frame, f32 [n_i,3] each; clouds_local: the same fragments
+    untransformed, or None) -> ({(i, j): rows int32 [P,2]}, corrs): keypoint_pairs for every pair of pair_schedule that passes
+    fragment_overlap (source i, target j, the whole clouds: see fragment_overlap on subsampling), the others skipped as in
+    run_keypoint.py:124.  corrs is None without clouds_local, else the list of f32 [P,2,3] fragment-frame coordinates, in the
+    order of the dictionary: [:,0] = clouds_local[i][rows[:,0]], [:,1] = clouds_local[j][rows[:,1]] -- what
+    vgtk.pc.pack_correspondences takes.  Every fragment is indexed once, for all the pairs it takes part in; the gate reads one
+    bool per pair back to the host."""
+    if not isinstance(clouds_world, (list, tuple)):
+        raise TypeError(f"clouds_world must be a list of [n,3] tensors, got {type(clouds_world).__name__}")
+    F = len(clouds_world)
+    if clouds_local is not None and len(clouds_local) != F:
+        raise ValueError(f"clouds_local must hold the same {F} fragments, got {len(clouds_local)}")
+    for k in range(F):
+        _tensor(clouds_world[k], f"clouds_world[{k}]", (None, 3), torch.float32)
+        if clouds_local is not None:
+            _tensor(clouds_local[k], f"clouds_local[{k}]", (clouds_world[k].shape[0], 3), torch.float32)
+    _lib.same_device(*clouds_world, *(clouds_local or ()))
+    R = max(float(margin), raw_radius(voxel_size))
+    grids = {}
+
+    def grid(k):
+        if k not in grids:
+            grids[k] = PointGrid(clouds_world[k], R)
+        return grids[k]
+
+    rows, corrs = {}, None if clouds_local is None else []
+    for i, j in pair_schedule(F, stride, window):
+        if not bool(fragment_overlap(grid(i).points, grid(j), margin, ratio)[1]):
+            continue
+        r = keypoint_pairs(grid(i), grid(j), voxel_size=voxel_size, isolation_radius=isolation_radius,
+                           match_radius=match_radius).rows
+        rows[(i, j)] = r
+        if corrs is not None:
+            r64 = r.to(torch.int64)
+            corrs.append(torch.stack((clouds_local[i][r64[:, 0]], clouds_local[j][r64[:, 1]]), dim=1))
+    return rows, corrs

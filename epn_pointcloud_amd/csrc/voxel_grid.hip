@@ -19,31 +19,20 @@
 // The sums are integers and the minimum is a minimum: nothing depends on arrival order, so the result is bitwise repeatable.
 // Every probe loop is bounded by the capacity (the load factor is at most 1/2, so a free slot exists); no workgroup waits on
 // another, nothing spins, no floating-point atomics.  Every table index is masked by capacity - 1, every point index is below n
-// and every rank below M <= n (the caller allocates n rows).
-#include <climits>
-#include <cmath>
-
-#include "epn_common.h"
+// and every rank below M <= n (the caller allocates n rows).  The cell rule, the hash probing, the bounds reduction and the
+// workgroup scans live in cell_hash.h, which point_grid.hip shares.
+#include "cell_hash.h"
 
 namespace {
 
-constexpr int VT = 256;                  // threads per workgroup = points per scan tile
-constexpr int VW = VT / 64;              // waves
-constexpr int64_t VOX_MAX_N = 1 << 22;
-constexpr unsigned long long VOX_EMPTY = ~0ull;
-constexpr unsigned long long VOX_HASH = 0x9E3779B97F4A7C15ull;
-constexpr unsigned FLAG_COORD = 1u, FLAG_INDEX = 2u, FLAG_TABLE = 4u;
+using namespace epn_cells;               // the cell rule, the hash table and the workgroup scans: shared with point_grid.hip
+
+constexpr int64_t VOX_MAX_N = MAX_N;
 
 struct Slot {                            // 48 bytes: one voxel
     unsigned long long key;
     unsigned long long sum[3];           // two's complement sums of llrint(coordinate * 2^32)
     int count, first, row, pad;
-};
-
-struct Head {                            // the workspace's first 64 bytes
-    unsigned lo[3];                      // order-preserving image of the fp32 minima
-    unsigned flags;
-    unsigned pad[12];
 };
 
 struct Layout {
@@ -53,8 +42,7 @@ struct Layout {
 
 Layout layout(int64_t n) {
     Layout L;
-    L.log2cap = 7;
-    while (((int64_t)1 << L.log2cap) < 2 * n) ++L.log2cap;
+    L.log2cap = log2_capacity(n);
     L.cap = (size_t)1 << L.log2cap;
     L.slots = sizeof(Head);
     L.pslot = L.slots + L.cap * sizeof(Slot);
@@ -63,32 +51,12 @@ Layout layout(int64_t n) {
     return L;
 }
 
-// floats order like these unsigned integers (-0 below +0, which changes no voxel index)
-__device__ __forceinline__ unsigned ordered(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unordered(unsigned u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-
-// a point's coordinates, and whether it is kept (all three finite)
-__device__ __forceinline__ bool load_point(const float *__restrict__ pc, int i, float &x, float &y, float &z) {
-    x = pc[3 * (size_t)i];
-    y = pc[3 * (size_t)i + 1];
-    z = pc[3 * (size_t)i + 2];
-    return isfinite(x) && isfinite(y) && isfinite(z);
-}
-
 __global__ __launch_bounds__(VT) void voxel_init_kernel(Head *head, Slot *slots, unsigned cap) {
     const unsigned e = blockIdx.x * VT + threadIdx.x;
-    if (e == 0) {
-        head->lo[0] = head->lo[1] = head->lo[2] = ordered(INFINITY);
-        head->flags = 0u;
-    }
+    if (e == 0) init_head(head);
     if (e >= cap) return;
     Slot s;
-    s.key = VOX_EMPTY;
+    s.key = EMPTY;
     s.sum[0] = s.sum[1] = s.sum[2] = 0ull;
     s.count = 0;
     s.first = INT_MAX;
@@ -98,40 +66,17 @@ __global__ __launch_bounds__(VT) void voxel_init_kernel(Head *head, Slot *slots,
 }
 
 __global__ __launch_bounds__(VT) void voxel_bounds_kernel(const float *__restrict__ pc, int n, Head *head) {
-    __shared__ float wmin[VW][3];
-    __shared__ int wfar[VW];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = (int)blockIdx.x * VT + tid;
+    const int i = (int)blockIdx.x * VT + (int)threadIdx.x;
     float x = INFINITY, y = INFINITY, z = INFINITY;
     int far = 0;
     if (i < n) {
         float px, py, pz;
         if (load_point(pc, i, px, py, pz)) {
             x = px; y = py; z = pz;
-            far = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)) > 256.0f;
+            far = too_far(px, py, pz);
         }
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        x = fminf(x, __shfl_xor(x, s, 64));
-        y = fminf(y, __shfl_xor(y, s, 64));
-        z = fminf(z, __shfl_xor(z, s, 64));
-        far |= __shfl_xor(far, s, 64);
-    }
-    if (lane == 0) { wmin[wave][0] = x; wmin[wave][1] = y; wmin[wave][2] = z; wfar[wave] = far; }
-    __syncthreads();
-    if (tid < 3) {
-        float m = wmin[0][tid];
-#pragma unroll
-        for (int w = 1; w < VW; ++w) m = fminf(m, wmin[w][tid]);
-        if (m < INFINITY) atomicMin(&head->lo[tid], ordered(m));
-    }
-    if (tid == 3) {
-        int f = 0;
-#pragma unroll
-        for (int w = 0; w < VW; ++w) f |= wfar[w];
-        if (f) atomicOr(&head->flags, FLAG_COORD);
-    }
+    bounds_body(x, y, z, far, head);
 }
 
 __global__ __launch_bounds__(VT) void voxel_insert_kernel(const float *__restrict__ pc, int n, double voxel_size, int log2cap,
@@ -140,22 +85,14 @@ __global__ __launch_bounds__(VT) void voxel_insert_kernel(const float *__restric
     if (i >= n) return;
     float x, y, z;
     int mine = -1;
-    if (load_point(pc, i, x, y, z) && !(fmaxf(fmaxf(fabsf(x), fabsf(y)), fabsf(z)) > 256.0f)) {
-        const double half = 0.5 * voxel_size;
-        const double ix = floor(((double)x - ((double)unordered(head->lo[0]) - half)) / voxel_size);
-        const double iy = floor(((double)y - ((double)unordered(head->lo[1]) - half)) / voxel_size);
-        const double iz = floor(((double)z - ((double)unordered(head->lo[2]) - half)) / voxel_size);
-        if (!(ix < 2097152.0 && iy < 2097152.0 && iz < 2097152.0)) {
+    if (load_point(pc, i, x, y, z) && !too_far(x, y, z)) {
+        const double ix = cell_axis(x, head->lo[0], voxel_size);
+        const double iy = cell_axis(y, head->lo[1], voxel_size);
+        const double iz = cell_axis(z, head->lo[2], voxel_size);
+        if (!(ix < INDEX_END && iy < INDEX_END && iz < INDEX_END)) {
             atomicOr(&head->flags, FLAG_INDEX);
         } else {
-            const unsigned long long key = ((unsigned long long)ix << 42) | ((unsigned long long)iy << 21) | (unsigned long long)iz;
-            const unsigned mask = (1u << log2cap) - 1u;
-            unsigned s = (unsigned)((key * VOX_HASH) >> (64 - log2cap));
-            for (unsigned probe = 0; probe <= mask; ++probe, s = (s + 1u) & mask) {
-                unsigned long long k = __hip_atomic_load(&slots[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (k == VOX_EMPTY) k = atomicCAS(&slots[s].key, VOX_EMPTY, key);
-                if (k == VOX_EMPTY || k == key) { mine = (int)s; break; }
-            }
+            mine = claim_slot(slots, cell_key(ix, iy, iz), log2cap);
             if (mine < 0) {
                 atomicOr(&head->flags, FLAG_TABLE);        // cannot happen at a load factor <= 1/2; loud if it ever does
             } else {
@@ -195,32 +132,9 @@ __global__ __launch_bounds__(VT) void voxel_count_kernel(const int *__restrict__
 
 // one workgroup: bcnt[0..nb) -> exclusive prefix sums in place, VT entries per pass with a running carry
 __global__ __launch_bounds__(VT) void voxel_scan_kernel(int *bcnt, int nb, const Head *head, int32_t *__restrict__ status) {
-    __shared__ int wsum[VW];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int carry = 0;
-    for (int base = 0; base < nb; base += VT) {
-        const int e = base + tid;
-        const int v = e < nb ? bcnt[e] : 0;
-        int incl = v;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int up = __shfl_up(incl, s, 64);
-            if (lane >= s) incl += up;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < VW; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            total += wsum[w];
-        }
-        if (e < nb) bcnt[e] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();                                   // wsum is rewritten by the next pass
-    }
-    if (tid == 0) {
-        status[0] = carry;
+    const int total = scan_sums(bcnt, nb);
+    if (threadIdx.x == 0) {
+        status[0] = total;
         status[1] = (int32_t)head->flags;
     }
 }

@@ -112,6 +112,66 @@ def voxel_downsample(pc, voxel_size):
     return centroids[:m], counts[:m], first_idx[:m], point_voxel
 
 
+MAX_GRID_POINTS = 2 ** 22
+MIN_GRID_RADIUS = 2.0 ** -60
+
+
+def point_grid_build(ref, max_radius, valid=None):
+    """(ref f[n,3], float max_radius, valid u8/bool [n] or None) -> (workspace int64 tensor, status int32 [2] = {kept, flags}
+    on the device, or None when n == 0): the hashed grid of one cloud with its points sorted by cell, for point_grid_nn with
+    any radius <= max_radius (epn_point_grid_build_f32, include/epn_so3conv.h; no counterpart among the reference's
+    extensions -- it replaces the host trees of SPConvNets/datasets/preprocess/run_keypoint.py).  Nothing is read back: the
+    caller looks at status[1] (the flags of voxel_downsample) when it wants to."""
+    from ...data import _tensor
+    lib = _lib.get_lib()
+    ref = _tensor(ref, "ref", (None, 3), torch.float32)
+    n = ref.shape[0]
+    if valid is not None:
+        valid = _tensor(valid, "valid", (n,), (torch.uint8, torch.bool))
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+    r = float(max_radius)
+    if not (np.isfinite(r) and r >= MIN_GRID_RADIUS):
+        raise ValueError(f"max_radius must be finite and >= 2^-60, got {max_radius}")
+    if n > MAX_GRID_POINTS:
+        raise ValueError(f"a point grid takes at most 2^22 points, got {n}")
+    _lib.same_device(ref, valid)
+    ws_bytes = int(lib.epn_point_grid_workspace_bytes(n))
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=ref.device)
+    status = torch.empty((2,), dtype=torch.int32, device=ref.device) if n else None
+    _lib.check(lib.epn_point_grid_build_f32(_lib.dev_ptr(ref, "ref"), n, _lib.dev_ptr(valid, "valid", torch.uint8), r,
+                                            ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8,
+                                            _lib.dev_ptr(status, "status", torch.int32), _lib.stream_of(ref)), "point_grid_build")
+    return ws, status
+
+
+def point_grid_nn(workspace, n, queries, radius, exclude_row=False, count=False):
+    """(workspace from point_grid_build of n points, queries f[m,3], float radius <= the build's max_radius) -> (nn_idx int32
+    [m], nn_d2 f[m][, hits int32 [1]]): per query the nearest point of the grid within radius -- the smallest fp32 squared
+    distance, the lowest row on a tie -- or -1 and +inf; exclude_row skips the candidate at the query's own row (m == n);
+    hits, with count, is the number of queries that found one, on the device (epn_point_grid_nn_f32)."""
+    from ...data import _tensor
+    lib = _lib.get_lib()
+    workspace = _tensor(workspace, "workspace", (None,), torch.int64)
+    queries = _tensor(queries, "queries", (None, 3), torch.float32)
+    n, m, r = int(n), queries.shape[0], float(radius)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"radius must be finite and > 0, got {radius}")
+    if m > MAX_GRID_POINTS:
+        raise ValueError(f"a call takes at most 2^22 queries, got {m}")
+    if exclude_row and m != n:
+        raise ValueError(f"exclude_row needs the grid's own {n} points as queries, got {m}")
+    _lib.same_device(workspace, queries)
+    nn_idx = torch.empty((m,), dtype=torch.int32, device=queries.device)
+    nn_d2 = torch.empty((m,), dtype=torch.float32, device=queries.device)
+    hits = torch.empty((1,), dtype=torch.int32, device=queries.device) if count else None
+    _lib.check(lib.epn_point_grid_nn_f32(ctypes.c_void_p(workspace.data_ptr()), n, _lib.dev_ptr(queries, "queries"), m, r,
+                                         int(bool(exclude_row)), _lib.dev_ptr(nn_idx, "nn_idx", torch.int32),
+                                         _lib.dev_ptr(nn_d2, "nn_d2"), _lib.dev_ptr(hits, "hits", torch.int32),
+                                         _lib.stream_of(queries)), "point_grid_nn")
+    return (nn_idx, nn_d2, hits) if count else (nn_idx, nn_d2)
+
+
 def _scene_tables(frag_off, pairs, device):
     """Host copies (contiguous numpy: what the library's argument checks read) and device copies (what its kernels read) of a
     scene's tables, with out_off / tgt_off computed from them (include/epn_so3conv.h, "Scene tables")."""

@@ -352,6 +352,67 @@ int epn_voxel_downsample_f32(const float *pc, int64_t n, double voxel_size, floa
                              int32_t *first_idx, int32_t *point_voxel, int32_t *status, void *workspace,
                              size_t workspace_bytes, epn_stream_t stream);
 
+/* Point grid: the nearest point of ONE cloud within a bound, for 3-D queries (csrc/point_grid.hip).  It is the one
+ * primitive of the reference's keypoint stage (SPConvNets/datasets/preprocess/run_keypoint.py), which runs it on the host:
+ * sklearn's NearestNeighbors in test_scenes_overlap (:98-112), in cross_filtering_via_fpfh (:30-37, :66-67) and in the map back to
+ * raw rows (:131-138), and open3d's radius search behind compute_fpfh_feature (:47-48), of which only "is there another point
+ * within the radius" survives (:58-59).
+ *
+ * epn_point_grid_build_f32: ref f32[n,3] (row-major), ref_valid u8[n] or NULL, max_radius -> the grid, in the caller's workspace,
+ *   and status i32[2] = {kept, flags} on the device.
+ *   participation   a reference point takes part when all three coordinates are finite and ref_valid is NULL or its byte is
+ *                   non-zero.  kept = the number of points in the grid.
+ *   cell            edge = max_radius * (1 + 2^-10) in fp64.  Index, key, hash table and range flags are exactly
+ *                   epn_voxel_downsample_f32's with voxel_size = edge and "kept" read as "participating": lo = per-axis fp32
+ *                   minimum, ix = floor(((double)x - ((double)lo - 0.5 * edge)) / edge), key = ix << 42 | iy << 21 | iz,
+ *                   capacity the smallest power of two >= max(2n, 128), home slot (key * 0x9E3779B97F4A7C15) >> (64 -
+ *                   log2(capacity)), linear probing with wrap-around; flags bit 0: a participating |coordinate| > 256, bit 1: an
+ *                   index >= 2^21 (bit 2: the table overflowed, which the load factor excludes).  With flags != 0 the grid is
+ *                   not to be queried (such points are left out of it; a query stays inside the workspace all the same).
+ *   records         the points are counting-sorted by cell into 16-byte records {x, y, z, row}: per-cell counts (integer
+ *                   atomics), one scan over the table's slots (per-tile sums of 256 slots, one workgroup that scans the sums 256
+ *                   at a time, the offsets), a scatter through returned integer atomicAdd cursors.  The order of the records
+ *                   inside a cell is free and no output of either entry depends on it; the workspace's bytes are not part of
+ *                   the contract.
+ *   Why 27 cells suffice: let p be admissible for a query q, that is d2 <= r2 below with radius <= max_radius, and take one axis.
+ *     fl(dx * dx) <= d2 (adding non-negative terms and rounding never goes below a representable term), r2 <= radius^2 (1 +
+ *     2^-24), and fl(dx * dx) >= (p - q)^2 (1 - 2^-24)^3 unless it underflows, which needs |p - q| < 2^-63 (hence max_radius >=
+ *     2^-60).  So |p - q| <= max_radius (1 + 2^-22) <= edge (1 - 2^-11): the exact quotients (x - vmin) / edge of p and q differ by
+ *     less than 1 - 2^-11.  The computed ones are each within 2^21 * 2^-51 = 2^-30 of the exact ones (two fp64 roundings on a
+ *     value below 2^21; vmin is the same fp64 number for both), so they differ by less than 1 and their floors by at most 1.
+ *   Workspace: epn_point_grid_workspace_bytes(n) bytes (host-only; 0 outside 0 <= n <= 2^22), 16-byte aligned; initialised by
+ *   the call itself.  Seven launches; nothing depends on arrival order but the order inside a cell.
+ *   0 <= n <= 2^22, max_radius finite and >= 2^-60, a large enough workspace, and ref and status when n > 0: EPN_EINVAL
+ *   otherwise, decided before any HIP runtime call.  n == 0 builds an empty grid: it launches nothing, leaves status untouched,
+ *   and every query on it answers -1.
+ *
+ * epn_point_grid_nn_f32: the grid of a build (the same workspace address and n), qry f32[m,3], radius -> nn_idx i32[m],
+ *   nn_d2 f32[m], hits i32[1] or NULL.
+ *   answer          among the points of the grid with d2 <= r2, the one with the smallest d2, on a tie the lowest row:
+ *                   nn_idx = its row in ref, nn_d2 = its d2; -1 and +inf when there is none.
+ *                   d2 = (dx*dx + dy*dy) + dz*dz, dx = p.x - q.x, every operation individually rounded in fp32 (no fma), as
+ *                   epn_radius_patches_f32's membership test; r2 = (float)(radius * radius), the product taken in fp64.
+ *   exclude_row     1: the candidate whose row equals the query's own index is skipped (a cloud searched against itself, m == n
+ *                   required; a duplicate of the point at another row is still found, with d2 = 0).  0: nothing is skipped.
+ *   no answer       a query with a non-finite coordinate reads no cell and gets -1.  A cell whose index is outside [0, 2^21) on
+ *                   an axis holds no point and is not looked up, so a query far outside the cloud gets -1 as well.
+ *   hits            the number of queries with nn_idx >= 0: zeroed on the stream by a one-wave launch of the library's own (no
+ *                   memset), then one integer atomicAdd per workgroup of the query.
+ *   One wave per query, four per workgroup: lanes 0..26 look up the 27 cells, the wave strides over their records with 16-byte
+ *   loads, and the best (d2 bits << 32 | row, one 64-bit key: d2 >= 0, so its bits order like its value) is the minimum over the
+ *   wave.  Integer minima and sums only: two runs are bitwise equal.  No host synchronisation: build and query can be captured
+ *   into a HIP graph on one stream.
+ *   The library remembers (n, max_radius) of the last build per workspace address on the host (at most 2^16 addresses; when a
+ *   build would exceed that, the older entries are forgotten and their grids must be built again).
+ *   0 <= n, m <= 2^22, radius finite, 0 < radius <= max_radius of the build, exclude_row 0 or 1 and m == n with 1, a workspace
+ *   address and n that a build has been called with, and qry, nn_idx, nn_d2 when m > 0: EPN_EINVAL otherwise, decided before any
+ *   HIP runtime call.  m == 0 succeeds (hits, if given, becomes 0). */
+size_t epn_point_grid_workspace_bytes(int64_t n);
+int epn_point_grid_build_f32(const float *ref, int64_t n, const uint8_t *ref_valid, double max_radius, void *workspace,
+                             size_t workspace_bytes, int32_t *status, epn_stream_t stream);
+int epn_point_grid_nn_f32(const void *workspace, int64_t n, const float *qry, int64_t m, double radius, int exclude_row,
+                          int32_t *nn_idx, float *nn_d2, int32_t *hits, epn_stream_t stream);
+
 /* Rotation estimation: what turns RegSO3ConvModel's head output into a rotation, the labels a training step needs and the
  * angular error the reference reports.  All tensors are contiguous device memory, float or int32; anchors
  * f32[A,3,3], 1 <= A <= 64.  Arithmetic is fp64 on the fp32 inputs and every output is rounded once to fp32.  One wave per
