@@ -18,7 +18,10 @@
 // at the LDS store rate: `ds_add_u32` 4.1 cycles, `ds_add_u64` 6.2 cycles per wave instruction -- 31 x faster.  So the
 // accumulators are 64-bit fixed point:
 //   * unit = 2^-s with s chosen per call from a device scalar max|dG| and the largest slot multiplicity of the index table so
-//     that every single contribution is below 2^50 units; a destination sums at most p2 <= 4096 contributions: below 2^62.
+//     that what ONE output point sends to a destination is below 2^50 units -- one contribution carrying its multiplicity where
+//     the slots a row keeps name distinct points, up to nn slots' worth where they do not (a row that is not cyclic, or a
+//     cyclic one whose period holds a point twice: such a row reports nn as its multiplicity); a destination hears from at
+//     most p2 <= 4096 output points: below 2^62.
 //   * fp32 -> fixed point in THREE instructions through the double-precision adder (full rate on this part):
 //     bits(double(x) + 1.5 * 2^52) - bits(1.5 * 2^52), where the second operand has a zero low word -- v_cvt_f64_f32,
 //     v_add_f64, v_add_u32 on the high word.  Round to nearest even, symmetric in sign.
@@ -54,7 +57,8 @@ constexpr int UC_LDS_MAX = 160 * 1024;     // LDS of one workgroup: the whole CU
 //                                   -- the S-MFMA operand of lane (x, j) is entry c = j, its accumulator start entry c = 4
 // Multiplicity as load_hood (inter_device.h): the ball query pads a row that found cnt < nn neighbours by repeating them
 // cyclically (vgtk/vgtk/cuda/grouping_cuda_kernel.cu:100-104); the first occurrence carries the number of slots holding that
-// point, the repeats (and slots without a point) 0 -- their weights come out as relu(0) = 0.  mulmax: largest multiplicity.
+// point, the repeats (and slots without a point) 0 -- their weights come out as relu(0) = 0.  mulmax: largest multiplicity;
+// a row whose KEPT slots name a point more than once counts as nn there.
 constexpr int UC_PTS = 8;                  // output points per wave of the table kernel
 __global__ __launch_bounds__(256) void uc_slots_kernel(const int32_t *__restrict__ idx, const float *__restrict__ xyz,
                                                        const float *__restrict__ new_xyz, long long npts, int p1, int p2, int nn, int ew,
@@ -75,6 +79,7 @@ __global__ __launch_bounds__(256) void uc_slots_kernel(const int32_t *__restrict
     bool valid[UC_PTS];
     unsigned mul[UC_PTS];
     float g[UC_PTS][3], cc[UC_PTS][3];
+    int kept[UC_PTS];                                         // slots the row keeps: its period if it is cyclic, else nn (wave-uniform)
 #pragma unroll
     for (int i = 0; i < UC_PTS; ++i) {
         const long long pt = pt0 + i < npts ? pt0 + i : npts - 1;
@@ -89,12 +94,26 @@ __global__ __launch_bounds__(256) void uc_slots_kernel(const int32_t *__restrict
         if (__ballot(bad) != 0ull) cnt = nn;
         valid[i] = q[i] >= 0 && q[i] < p1;
         mul[i] = (valid[i] && lane < cnt) ? (unsigned)((nn - 1 - lane) / cnt + 1) : 0u;
+        kept[i] = cnt;
         const float *s = xyz + bb * 3 * p1, *c = new_xyz + bb * 3 * p2;
         const int qq = valid[i] ? q[i] : 0;
         g[i][0] = s[qq]; g[i][1] = s[p1 + qq]; g[i][2] = s[2 * p1 + qq];
         cc[i][0] = c[pp]; cc[i][1] = c[p2 + pp]; cc[i][2] = c[2 * p2 + pp];
     }
+    // The slots a row KEEPS may still name a point more than once: [3, 5, 3, 3, ...] is not cyclic and keeps every slot;
+    // [1, 2, 2, 1, 2, 2, ...] is cyclic and keeps a period that holds point 2 twice.  Such slots stay apart, one contribution
+    // each, but they meet in ONE accumulator: the row reports nn to mulmax -- all its slots may name that point -- so that what
+    // an output point sends to a destination stays below 2^50 units in total.  Kept lane l against lanes l + 1 .. l + 32
+    // (mod 64) meets every pair of kept slots.
     unsigned m = 0;
+#pragma unroll
+    for (int i = 0; i < UC_PTS; ++i) {
+        const int key = mul[i] ? q[i] : -1 - lane;                // (slots that are not kept or name no point: distinct keys)
+        const int reach = kept[i] - 1 < 32 ? kept[i] - 1 : 32;
+        bool dup = false;
+        for (int o = 1; o <= reach; ++o) dup |= key == __shfl(key, (lane + o) & 63, 64);
+        if (__ballot(dup) != 0ull) m = (unsigned)nn;
+    }
 #pragma unroll
     for (int i = 0; i < UC_PTS; ++i) {
         const long long pt = pt0 + i < npts ? pt0 + i : npts - 1;

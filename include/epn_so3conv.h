@@ -1295,12 +1295,16 @@ int epn_inter_bwd_data_f16x2_f32(const epn_inter_desc *d, const float *grad_out_
  * grad_feats_cl; may BE grad_feats_cl; or NULL) is folded into the write-out, and the sum does not depend on the order in which
  * waves arrive: bitwise repeatable.
  * Fixed point: unit = max|grad_grouped| * 2^-(43 .. 50) (from the device scalar *dg_amax and the largest multiplicity of the
- * index table; every contribution is rounded ONCE to the unit, the sum is exact, one rounding to the output type).  dg_amax
+ * index table; every contribution is rounded ONCE to the unit, the sum is exact, one rounding to the output type).  The index
+ * table may be arbitrary: the ball query's cyclic padding is folded into multiplicities, and a row whose remaining slots (all of
+ * them if it is not cyclic, one period if it is) still name a point more than once counts with multiplicity nn (those slots are
+ * summed one by one, the unit is coarser, down to 2^-39 of the maximum), so that the 64-bit sum of a destination stays below
+ * 2^62 units for every table with p2 <= 4096.  dg_amax
  * NULL: the entry takes the maximum itself (one more pass over grad_grouped).  An UNDERSTATED maximum makes contributions leave
  * the representable range: such a workgroup writes NaN to its rows and bumps a sticky device counter
  * (epn_inter_ungroup_cloud_range_count; reset != 0 clears it), as does a non-finite grad_grouped.
  * Shapes (epn_..._ok): the MFMA grouping's (cin % 16 == 0, ks % 4 == 0, ks <= 32, nn <= 64), p2 <= 4096, and p1 small enough
- * for (p1 + 4) * 16 * 8 bytes of accumulators (p1 <= 1148). */
+ * for (p1 + 4) * 16 * 8 bytes of accumulators (p1 <= 1275). */
 int epn_inter_ungroup_cloud_ok(const epn_inter_desc *d);
 size_t epn_inter_ungroup_cloud_workspace_bytes(const epn_inter_desc *d);
 int epn_inter_ungroup_cloud_f32(const epn_inter_desc *d, const float *grad_grouped, const float *dg_amax, float *grad_feats_cl,
