@@ -1,6 +1,6 @@
 // Adam over every parameter of a model in two launches for gfx950: the optimiser of the three trainers
 // (vgtk/vgtk/app/trainer.py:162-168, optim.Adam driven by vgtk.LearningRateScheduler).  Specification: include/epn_so3conv.h
-// (epn_adam_step_f32), DESIGN.md 3.1i.  The arguments arrive checked (c_api.hip).
+// (epn_adam_step_f32), DESIGN.md 3.1i.
 //
 // The flat index space 0..n-1 is cut into chunks of ADAM_SPAN = 1024 elements; workgroup b owns the contiguous chunks
 // [b K, (b + 1) K) with K = ceil(chunks / min(chunks, 2048)), so the partition depends on n alone.  Thread t of a chunk owns the
@@ -20,8 +20,7 @@
 // one rounding per stored value; no float atomics, no ticket, no grid barrier, no allocation, no host synchronisation.
 #include <cmath>
 
-#include "conv_internal.h"
-#include "epn_common.h"
+#include "epn_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -56,20 +55,6 @@ Plan make_plan(long long n) {
     return p;
 }
 
-// sum over the workgroup in a fixed order: every thread's value into LDS, halved with a barrier per level
-template <typename T>
-__device__ __forceinline__ T block_sum(T x, T *buf) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    buf[tid] = x;
-    __syncthreads();
-    for (int s = FT / 2; s > 0; s >>= 1) {
-        if (tid < s) buf[tid] += buf[tid + s];
-        __syncthreads();
-    }
-    return buf[0];
-}
-
 __global__ __launch_bounds__(FT) void adam_norm_kernel(const float *__restrict__ grad, long long n, int per_block, int wide,
                                                        double s, const int32_t *__restrict__ counters, Header *__restrict__ hdr,
                                                        double *__restrict__ partial, unsigned long long *__restrict__ bad) {
@@ -97,8 +82,8 @@ __global__ __launch_bounds__(FT) void adam_norm_kernel(const float *__restrict__
             nbad += isfinite(g[j]) ? 0 : 1;
         }
     }
-    const double sum = block_sum(acc, buf);
-    const unsigned long long cnt = block_sum(nbad, cbuf);
+    const double sum = epn_block_sum<FT>(acc, buf);
+    const unsigned long long cnt = epn_block_sum<FT>(nbad, cbuf);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = sum;
         bad[blockIdx.x] = cnt;
@@ -139,8 +124,8 @@ __global__ __launch_bounds__(FT) void adam_update_kernel(const unsigned long lon
         part += partial[j];
         nb += bad[j];
     }
-    const double sumsq = block_sum(part, buf);
-    const unsigned long long nbad = block_sum(nb, cbuf);
+    const double sumsq = epn_block_sum<FT>(part, buf);
+    const unsigned long long nbad = epn_block_sum<FT>(nb, cbuf);
     const double norm = sqrt(sumsq);
     const bool skip = nbad > 0 || !isfinite(norm);
     double c = 1.0;
@@ -253,19 +238,40 @@ __global__ __launch_bounds__(FT) void adam_update_kernel(const unsigned long lon
     }
 }
 
-}  // namespace
-
-namespace epn {
-
 size_t adam_workspace_bytes(long long n) {
     (void)n;                                  // the partials are bounded by the grid, not by n
     return WS_BYTES;
 }
 
-int launch_adam_step(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n, const float *grad,
-                     float *exp_avg, float *exp_avg_sq, const float *lr, double beta1, double beta2, double eps,
-                     double weight_decay, double grad_scale, double max_norm, int32_t *counters, float *info, void *workspace,
-                     hipStream_t st) {
+bool adam_sizes_ok(int nseg, long long n) { return nseg >= 1 && nseg <= 65536 && n >= 1 && n < (1LL << 40) && nseg <= n; }
+
+}  // namespace
+
+extern "C" size_t epn_adam_workspace_bytes(long long n) { return adam_workspace_bytes(n); }
+
+extern "C" int epn_adam_check_plan(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n) {
+    if (!(nseg >= 1 && nseg <= 65536 && n >= 1 && n < (1LL << 40))) return EPN_EINVAL;
+    if (!seg_param || !seg_off) return EPN_ENULL;
+    if (seg_off[0] != 0 || seg_off[nseg] != n) return EPN_EINVAL;
+    for (int s = 0; s < nseg; ++s)
+        if (seg_off[s + 1] <= seg_off[s] || seg_param[s] == 0 || (seg_param[s] & 3) != 0) return EPN_EINVAL;
+    return 0;
+}
+
+// Every refusal is decided before the first HIP runtime call.  Sizes and hyper-parameters first (EPN_EINVAL; the comparisons
+// are written so that a NaN fails them), then pointers (EPN_ENULL), then the workspace
+extern "C" int epn_adam_step_f32(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n,
+                                 const float *grad, float *exp_avg, float *exp_avg_sq, const float *lr, double beta1,
+                                 double beta2, double eps, double weight_decay, double grad_scale, double max_norm,
+                                 int32_t *counters, float *info, void *workspace, size_t workspace_bytes, epn_stream_t stream) {
+    if (!adam_sizes_ok(nseg, n)) return EPN_EINVAL;
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return EPN_EINVAL;
+    if (!(eps > 0.0 && eps < INFINITY) || !(weight_decay >= 0.0 && weight_decay < INFINITY)) return EPN_EINVAL;
+    if (!(grad_scale >= 0.0 && grad_scale < INFINITY) || max_norm != max_norm) return EPN_EINVAL;
+    if (!seg_param || !seg_off || !grad || !exp_avg || !exp_avg_sq || !lr || !counters || !info) return EPN_ENULL;
+    if (!workspace || workspace_bytes < adam_workspace_bytes(n) || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)
+        return EPN_EWORKSPACE;
+    hipStream_t st = epn_stream(stream);
     const Plan p = make_plan(n);
     Header *hdr = static_cast<Header *>(workspace);
     double *partial = reinterpret_cast<double *>(hdr + 1);
@@ -281,5 +287,3 @@ int launch_adam_step(const unsigned long long *seg_param, const long long *seg_o
     EPN_CHECK_LAUNCH();
     return 0;
 }
-
-}  // namespace epn

@@ -1,8 +1,8 @@
-// extern "C" entry points of libepn_so3conv.so for the convolution path (see include/epn_so3conv.h).
+// extern "C" entry points of libepn_so3conv.so for the convolution path (see include/epn_so3conv.h), and the library's own:
+// version, error strings, kernel policy and epn_last_kernel.  Every other stage keeps its entry points in its own file.
 // Dispatch: fused MFMA kernels when cin and cout are multiples of 16, generic kernels otherwise
 // (epn_set_kernel_policy(1) forces the generic path; used by the cross-check tests).
 #include <atomic>
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <cxxabi.h>
@@ -125,8 +125,6 @@ extern "C" size_t epn_inter_workspace_bytes(const epn_inter_desc *d) {
     InterWs w = inter_ws(d);
     // the generic path may be forced at run time, so always report the larger requirement when asked to
     if (force_generic() || d->dense_w) {
-        epn_inter_desc g = *d;
-        g.cin = d->cin; g.cout = d->cout;
         const size_t big = (size_t)d->b * d->p2 * d->na * d->cin * d->ks;
         return (w.big_off + rnd64(big)) * sizeof(float);
     }
@@ -603,105 +601,4 @@ extern "C" int epn_intra_so3conv_bwd_weight_f32(const float *feats_cl, const flo
         return launch_intra_bwd_weight_mfma(feats_cl, grad_out_cl, intra_idx, b, p, na, kn, cin, cout, grad_W, st);
     return launch_intra_bwd_weight_generic(feats_cl, grad_out_cl, intra_idx, (size_t)b * p, na, kn, cin, cout, grad_W,
                                            st);
-}
-
-// ModelNet training batches (modelnet_batch.hip): every argument is checked before the first HIP runtime call
-extern "C" int epn_modelnet_batch_f32(const float *points, int m, const int32_t *offsets, int b, const int64_t *ids,
-                                      int n_sample, uint64_t seed, int key_bits, int rot_mode, const float *R_in,
-                                      const float *anchors, int A, float *pc_out, float *pc_plain, int32_t *idx, float *R,
-                                      int32_t *R_label, float *R_res, int32_t *status, epn_stream_t stream) {
-    if (b < 0 || m < 0 || n_sample < 1 || n_sample > 8192 || key_bits < 1 || key_bits > 32) return EPN_EINVAL;
-    if (rot_mode < 0 || rot_mode > 2 || (rot_mode == 2 && !R_in)) return EPN_EINVAL;
-    if (anchors && (A < 1 || A > 64)) return EPN_EINVAL;
-    if (b == 0) return 0;
-    if (!offsets || !pc_out || !idx || !R || !status || (m > 0 && !points)) return EPN_EINVAL;
-    if (anchors && (!R_label || !R_res)) return EPN_EINVAL;
-    return launch_modelnet_batch(points, m, offsets, b, ids, n_sample, seed, key_bits, rot_mode, R_in, anchors, A, pc_out,
-                                 pc_plain, idx, R, R_label, R_res, status, epn_stream(stream));
-}
-
-// 3DMatch training batches (pair_batch.hip): sizes and scalars first, then B == 0, then pointers -- all before the first HIP
-// runtime call.  The grid is B * 2 * npt workgroups in x.
-extern "C" int epn_fragment_pair_batch_f32(const float *points, int m, const int32_t *offsets, int F, const int32_t *pairs, int B,
-                                           const float *corr, int C, const int32_t *corr_offsets, const double *poses,
-                                           const int64_t *ids, int n_sample, int npt, float radius, uint64_t seed, int key_bits,
-                                           int max_degree, int center, float *src, float *tgt, int32_t *idx, int32_t *counts,
-                                           int32_t *choice, float *T, float *R_aug, float *T_aug, int32_t *status,
-                                           epn_stream_t stream) {
-    if (B < 0 || F < 0 || m < 0 || C < 0 || n_sample < 1 || n_sample > 8192 || npt < 1 || npt > 4096) return EPN_EINVAL;
-    if (key_bits < 1 || key_bits > 32 || max_degree < 0 || max_degree > 360) return EPN_EINVAL;
-    if (!std::isfinite(radius) || !(radius > 0.0f) || (center != 0 && center != 1)) return EPN_EINVAL;
-    if ((long long)B * 2 * npt > 2147483647LL) return EPN_EINVAL;
-    if (B == 0) return 0;
-    if (!offsets || !pairs || !corr_offsets || (m > 0 && !points) || (C > 0 && !corr) || (F > 0 && !poses)) return EPN_EINVAL;
-    if (!src || !tgt || !idx || !counts || !choice || !T || !R_aug || !T_aug || !status) return EPN_EINVAL;
-    return launch_fragment_pair_batch(points, m, offsets, F, pairs, B, corr, C, corr_offsets, poses, ids, n_sample, npt, radius,
-                                      seed, key_bits, max_degree, center, src, tgt, idx, counts, choice, T, R_aug, T_aug, status,
-                                      epn_stream(stream));
-}
-
-// Classification loss and tallies (cls_loss.hip): every argument is checked before the first HIP runtime call.  Sizes first
-// (EPN_EINVAL), then pointers (EPN_ENULL); the attention set is absent as a whole (R == 0: its pointers are not looked at)
-static bool cls_rows_ok(int rows, int n) { return rows >= 1 && rows <= 65536 && n >= 1 && n <= 4096 && (long long)rows * n < (1LL << 31); }
-
-extern "C" int epn_cls_loss_f32(const float *logits, const int32_t *label, int B, int k, const float *att,
-                                const int32_t *att_label, int R, int A, const float *coef, float *row_ce, int32_t *pred,
-                                int32_t *flags, float *att_row_ce, int32_t *att_pred, int32_t *att_flags, float *scalars,
-                                epn_stream_t stream) {
-    if (!cls_rows_ok(B, k) || (R != 0 && !cls_rows_ok(R, A))) return EPN_EINVAL;
-    if (!logits || !label || !coef || !row_ce || !pred || !flags || !scalars) return EPN_ENULL;
-    if (R != 0 && (!att || !att_label || !att_row_ce || !att_pred || !att_flags)) return EPN_ENULL;
-    return launch_cls_loss(logits, label, B, k, att, att_label, R, A, coef, row_ce, pred, flags, att_row_ce, att_pred, att_flags,
-                           scalars, epn_stream(stream));
-}
-
-extern "C" int epn_cls_loss_bwd_f32(const float *upstream, const float *logits, const int32_t *label, const int32_t *flags, int B,
-                                    int k, const float *att, const int32_t *att_label, const int32_t *att_flags, int R, int A,
-                                    const float *coef, float *dlogits, float *datt, epn_stream_t stream) {
-    if (!cls_rows_ok(B, k) || (R != 0 && !cls_rows_ok(R, A))) return EPN_EINVAL;
-    if (!upstream || !logits || !label || !flags || !coef || !dlogits) return EPN_ENULL;
-    if (R != 0 && (!att || !att_label || !att_flags || !datt)) return EPN_ENULL;
-    return launch_cls_loss_bwd(upstream, logits, label, flags, B, k, att, att_label, att_flags, R, A, coef, dlogits, datt,
-                               epn_stream(stream));
-}
-
-extern "C" int epn_cls_tally_i32(const int32_t *pred, const int32_t *label, const int32_t *flags, const int32_t *att_pred,
-                                 const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
-                                 int32_t *anchor_table, int32_t *totals, epn_stream_t stream) {
-    if (B < 1 || B > 65536 || k < 1 || k > 4096) return EPN_EINVAL;
-    if (att_pred && (A < 1 || A > 4096)) return EPN_EINVAL;
-    if (!pred || !label || !flags || !confusion || !totals) return EPN_ENULL;
-    if (att_pred && (!att_flags || !anchor_table)) return EPN_ENULL;
-    return launch_cls_tally(pred, label, flags, att_pred, att_pred ? att_label : nullptr, att_flags, B, k, A, confusion,
-                            anchor_table, totals, epn_stream(stream));
-}
-
-// Adam step (adam_step.hip): every refusal is decided before the first HIP runtime call.  Sizes and hyper-parameters first
-// (EPN_EINVAL; the comparisons are written so that a NaN fails them), then pointers (EPN_ENULL), then the workspace
-static bool adam_sizes_ok(int nseg, long long n) { return nseg >= 1 && nseg <= 65536 && n >= 1 && n < (1LL << 40) && nseg <= n; }
-
-extern "C" size_t epn_adam_workspace_bytes(long long n) { return adam_workspace_bytes(n); }
-
-extern "C" int epn_adam_check_plan(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n) {
-    if (!(nseg >= 1 && nseg <= 65536 && n >= 1 && n < (1LL << 40))) return EPN_EINVAL;
-    if (!seg_param || !seg_off) return EPN_ENULL;
-    if (seg_off[0] != 0 || seg_off[nseg] != n) return EPN_EINVAL;
-    for (int s = 0; s < nseg; ++s)
-        if (seg_off[s + 1] <= seg_off[s] || seg_param[s] == 0 || (seg_param[s] & 3) != 0) return EPN_EINVAL;
-    return 0;
-}
-
-extern "C" int epn_adam_step_f32(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n,
-                                 const float *grad, float *exp_avg, float *exp_avg_sq, const float *lr, double beta1,
-                                 double beta2, double eps, double weight_decay, double grad_scale, double max_norm,
-                                 int32_t *counters, float *info, void *workspace, size_t workspace_bytes, epn_stream_t stream) {
-    if (!adam_sizes_ok(nseg, n)) return EPN_EINVAL;
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return EPN_EINVAL;
-    if (!(eps > 0.0 && eps < INFINITY) || !(weight_decay >= 0.0 && weight_decay < INFINITY)) return EPN_EINVAL;
-    if (!(grad_scale >= 0.0 && grad_scale < INFINITY) || max_norm != max_norm) return EPN_EINVAL;
-    if (!seg_param || !seg_off || !grad || !exp_avg || !exp_avg_sq || !lr || !counters || !info) return EPN_ENULL;
-    if (!workspace || workspace_bytes < adam_workspace_bytes(n) || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)
-        return EPN_EWORKSPACE;
-    return launch_adam_step(seg_param, seg_off, nseg, n, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
-                            grad_scale, max_norm, counters, info, workspace, epn_stream(stream));
 }

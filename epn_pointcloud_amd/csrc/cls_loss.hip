@@ -1,6 +1,6 @@
 // The classification network's training loss and evaluation tallies for gfx950: CrossEntropyLoss and AttentionCrossEntropyLoss
 // (vgtk/vgtk/loss.py:18-75) and the counting of SPConvNets/trainer_modelnet.py:138-210.  Specification: include/epn_so3conv.h
-// (epn_cls_loss_f32, epn_cls_loss_bwd_f32, epn_cls_tally_i32), DESIGN.md 3.1g.  The arguments arrive checked (c_api.hip).
+// (epn_cls_loss_f32, epn_cls_loss_bwd_f32, epn_cls_tally_i32), DESIGN.md 3.1g.
 //
 // The class term and the attention term are one problem twice: rows of n contiguous fp32 logits with one int32 label each.  A
 // launch takes a descriptor of the two row sets (the second may be empty) and serves both.
@@ -18,8 +18,7 @@
 #include <climits>
 #include <cmath>
 
-#include "conv_internal.h"
-#include "epn_common.h"
+#include "epn_reduce.h"
 
 namespace {
 
@@ -101,19 +100,6 @@ __global__ __launch_bounds__(FT) void cls_loss_rows_kernel(const RowSets d) {
     rs.flags[row] = (in_range ? 0 : FLAG_BAD_LABEL) | (finite ? 0 : FLAG_NONFINITE);
 }
 
-// sum over the workgroup in a fixed order: every thread's partial into LDS, halved with a barrier per level
-__device__ __forceinline__ double block_sum(double x, double *buf) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    buf[tid] = x;
-    __syncthreads();
-    for (int s = FT / 2; s > 0; s >>= 1) {
-        if (tid < s) buf[tid] += buf[tid + s];
-        __syncthreads();
-    }
-    return buf[0];
-}
-
 __global__ __launch_bounds__(FT) void cls_loss_finish_kernel(const RowSets d, const float *__restrict__ coef,
                                                              float *__restrict__ scalars) {
     __shared__ double buf[FT];
@@ -127,8 +113,8 @@ __global__ __launch_bounds__(FT) void cls_loss_finish_kernel(const RowSets d, co
             const int p = rs.pred[i];
             hit += (p >= 0 && p == rs.label[i]) ? 1.0 : 0.0;
         }
-        mean[w] = block_sum(sc, buf) / (double)rs.rows;
-        acc[w] = block_sum(hit, buf) / (double)rs.rows;
+        mean[w] = epn_block_sum<FT>(sc, buf) / (double)rs.rows;
+        acc[w] = epn_block_sum<FT>(hit, buf) / (double)rs.rows;
     }
     if (threadIdx.x == 0) {
         double loss = (double)coef[0] * mean[0];
@@ -214,13 +200,20 @@ RowSets row_sets(const float *logits, const int32_t *label, int B, int k, const 
     return d;
 }
 
+bool cls_rows_ok(int rows, int n) { return rows >= 1 && rows <= 65536 && n >= 1 && n <= 4096 && (long long)rows * n < (1LL << 31); }
+
 }  // namespace
 
-namespace epn {
-
-int launch_cls_loss(const float *logits, const int32_t *label, int B, int k, const float *att, const int32_t *att_label, int R,
-                    int A, const float *coef, float *row_ce, int32_t *pred, int32_t *flags, float *att_row_ce,
-                    int32_t *att_pred, int32_t *att_flags, float *scalars, hipStream_t st) {
+// Every argument is checked before the first HIP runtime call.  Sizes first (EPN_EINVAL), then pointers (EPN_ENULL); the
+// attention set is absent as a whole (R == 0: its pointers are not looked at)
+extern "C" int epn_cls_loss_f32(const float *logits, const int32_t *label, int B, int k, const float *att,
+                                const int32_t *att_label, int R, int A, const float *coef, float *row_ce, int32_t *pred,
+                                int32_t *flags, float *att_row_ce, int32_t *att_pred, int32_t *att_flags, float *scalars,
+                                epn_stream_t stream) {
+    if (!cls_rows_ok(B, k) || (R != 0 && !cls_rows_ok(R, A))) return EPN_EINVAL;
+    if (!logits || !label || !coef || !row_ce || !pred || !flags || !scalars) return EPN_ENULL;
+    if (R != 0 && (!att || !att_label || !att_row_ce || !att_pred || !att_flags)) return EPN_ENULL;
+    hipStream_t st = epn_stream(stream);
     const RowSets d = row_sets(logits, label, B, k, att, att_label, R, A, row_ce, pred, flags, nullptr, att_row_ce, att_pred,
                                att_flags, nullptr);
     const dim3 grid((unsigned)(d.blocks0 + epn_cdiv(R, RPB))), block(FT);
@@ -231,24 +224,29 @@ int launch_cls_loss(const float *logits, const int32_t *label, int B, int k, con
     return 0;
 }
 
-int launch_cls_loss_bwd(const float *upstream, const float *logits, const int32_t *label, const int32_t *flags, int B, int k,
-                        const float *att, const int32_t *att_label, const int32_t *att_flags, int R, int A, const float *coef,
-                        float *dlogits, float *datt, hipStream_t st) {
+extern "C" int epn_cls_loss_bwd_f32(const float *upstream, const float *logits, const int32_t *label, const int32_t *flags, int B,
+                                    int k, const float *att, const int32_t *att_label, const int32_t *att_flags, int R, int A,
+                                    const float *coef, float *dlogits, float *datt, epn_stream_t stream) {
+    if (!cls_rows_ok(B, k) || (R != 0 && !cls_rows_ok(R, A))) return EPN_EINVAL;
+    if (!upstream || !logits || !label || !flags || !coef || !dlogits) return EPN_ENULL;
+    if (R != 0 && (!att || !att_label || !att_flags || !datt)) return EPN_ENULL;
     const RowSets d = row_sets(logits, label, B, k, att, att_label, R, A, nullptr, nullptr, const_cast<int32_t *>(flags), dlogits,
                                nullptr, nullptr, const_cast<int32_t *>(att_flags), datt);
     const dim3 grid((unsigned)(d.blocks0 + epn_cdiv(R, RPB))), block(FT);
-    EPN_LAUNCH(cls_loss_bwd_kernel, grid, block, 0, st, d, upstream, coef);
+    EPN_LAUNCH(cls_loss_bwd_kernel, grid, block, 0, epn_stream(stream), d, upstream, coef);
     EPN_CHECK_LAUNCH();
     return 0;
 }
 
-int launch_cls_tally(const int32_t *pred, const int32_t *label, const int32_t *flags, const int32_t *att_pred,
-                     const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
-                     int32_t *anchor_table, int32_t *totals, hipStream_t st) {
-    EPN_LAUNCH(cls_tally_kernel, dim3((unsigned)epn_cdiv(B, FT)), dim3(FT), 0, st, pred, label, flags, att_pred, att_label, att_flags,
-               B, k, A, confusion, anchor_table, totals);
+extern "C" int epn_cls_tally_i32(const int32_t *pred, const int32_t *label, const int32_t *flags, const int32_t *att_pred,
+                                 const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
+                                 int32_t *anchor_table, int32_t *totals, epn_stream_t stream) {
+    if (B < 1 || B > 65536 || k < 1 || k > 4096) return EPN_EINVAL;
+    if (att_pred && (A < 1 || A > 4096)) return EPN_EINVAL;
+    if (!pred || !label || !flags || !confusion || !totals) return EPN_ENULL;
+    if (att_pred && (!att_flags || !anchor_table)) return EPN_ENULL;
+    EPN_LAUNCH(cls_tally_kernel, dim3((unsigned)epn_cdiv(B, FT)), dim3(FT), 0, epn_stream(stream), pred, label, flags, att_pred,
+               att_pred ? att_label : nullptr, att_flags, B, k, A, confusion, anchor_table, totals);
     EPN_CHECK_LAUNCH();
     return 0;
 }
-
-}  // namespace epn

@@ -1,4 +1,5 @@
-// Internal declarations shared by the convolution translation units of libepn_so3conv.so.
+// Internal declarations shared by the convolution translation units of libepn_so3conv.so: the workspace carve-up, the shape
+// predicates and the launchers that c_api.hip dispatches to.  Nothing of another stage is declared here.
 #pragma once
 #include "epn_common.h"
 
@@ -135,33 +136,5 @@ int launch_intra_bwd_data_mfma(const float *dOut, const int32_t *inv_idx, const 
                                int kn, int cin, int cout, float *dF, float *ws, hipStream_t st);
 int launch_intra_bwd_weight_mfma(const float *feats, const float *dOut, const int32_t *iidx, int b, int p, int na,
                                  int kn, int cin, int cout, float *dW, hipStream_t st);
-// modelnet_batch.hip: the arguments of epn_modelnet_batch_f32, already checked
-int launch_modelnet_batch(const float *points, int m, const int32_t *offsets, int b, const int64_t *ids, int n_sample,
-                          uint64_t seed, int key_bits, int rot_mode, const float *R_in, const float *anchors, int A,
-                          float *pc_out, float *pc_plain, int32_t *idx, float *R, int32_t *R_label, float *R_res, int32_t *status,
-                          hipStream_t st);
-// pair_batch.hip: the arguments of epn_fragment_pair_batch_f32, already checked
-int launch_fragment_pair_batch(const float *points, int m, const int32_t *offsets, int F, const int32_t *pairs, int B,
-                               const float *corr, int C, const int32_t *corr_offsets, const double *poses, const int64_t *ids,
-                               int n_sample, int npt, float radius, uint64_t seed, int key_bits, int max_degree, int center,
-                               float *src, float *tgt, int32_t *idx, int32_t *counts, int32_t *choice, float *T, float *R_aug,
-                               float *T_aug, int32_t *status, hipStream_t st);
-// cls_loss.hip: the arguments of epn_cls_loss_f32, epn_cls_loss_bwd_f32 and epn_cls_tally_i32, already checked
-int launch_cls_loss(const float *logits, const int32_t *label, int B, int k, const float *att, const int32_t *att_label, int R,
-                    int A, const float *coef, float *row_ce, int32_t *pred, int32_t *flags, float *att_row_ce,
-                    int32_t *att_pred, int32_t *att_flags, float *scalars, hipStream_t st);
-int launch_cls_loss_bwd(const float *upstream, const float *logits, const int32_t *label, const int32_t *flags, int B, int k,
-                        const float *att, const int32_t *att_label, const int32_t *att_flags, int R, int A, const float *coef,
-                        float *dlogits, float *datt, hipStream_t st);
-int launch_cls_tally(const int32_t *pred, const int32_t *label, const int32_t *flags, const int32_t *att_pred,
-                     const int32_t *att_label, const int32_t *att_flags, int B, int k, int A, int32_t *confusion,
-                     int32_t *anchor_table, int32_t *totals, hipStream_t st);
-
-// adam_step.hip: the arguments of epn_adam_step_f32, already checked; the bytes epn_adam_workspace_bytes reports
-size_t adam_workspace_bytes(long long n);
-int launch_adam_step(const unsigned long long *seg_param, const long long *seg_off, int nseg, long long n, const float *grad,
-                     float *exp_avg, float *exp_avg_sq, const float *lr, double beta1, double beta2, double eps,
-                     double weight_decay, double grad_scale, double max_norm, int32_t *counters, float *info, void *workspace,
-                     hipStream_t st);
 
 }  // namespace epn

@@ -25,7 +25,7 @@
 //             key_select.h, shared with patch_extract.hip.  idx is written to its global row and read back by the workgroup
 //             after a block-scope fence and a barrier.
 //   centroid  gather pass over the n_sample slots, FIXED REDUCTION ORDER in fp64: thread t adds slots t, t + 256, ... in
-//             ascending order; an xor tree over the wave (x += shfl_xor(x, s), s = 32..1: fp addition commutes, so every lane
+//             ascending order; an xor tree over the wave (epn_wave_sum, s = 32..1: fp addition commutes, so every lane
 //             ends with the same bits); the four wave sums are added in wave order by every thread.  The order depends on
 //             n_sample only and the geometry is fixed by the launcher: bitwise repeatable.  The same pass looks for non-finite
 //             coordinates.
@@ -38,8 +38,7 @@
 // read is offsets[b] + i with 0 <= i < n_b inside the checked [0, m].
 #include <cmath>
 
-#include "epn_common.h"
-#include "conv_internal.h"
+#include "epn_reduce.h"
 #include "key_select.h"
 #include "rotation_math.h"
 
@@ -53,18 +52,6 @@ struct BatchShared {
     float R[9];                    // the rounded rotation
     int flag[PW];
 };
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x += __shfl_xor(x, s, 64);
-    return x;
-}
-
-__device__ __forceinline__ double wave_max(double x) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x = fmax(x, __shfl_xor(x, s, 64));
-    return x;
-}
 
 // The cloud row of slot j: below un by construction; the clamp keeps the address inside the cloud whatever the row holds.
 __device__ __forceinline__ unsigned slot_row(const int32_t *irow, unsigned j, unsigned un) {
@@ -156,7 +143,7 @@ __global__ __launch_bounds__(PT) void modelnet_batch_kernel(const float *__restr
             bad |= !(std::isfinite(x) && std::isfinite(y) && std::isfinite(z));
             ax += (double)x; ay += (double)y; az += (double)z;
         }
-        ax = wave_sum(ax); ay = wave_sum(ay); az = wave_sum(az);
+        ax = epn_wave_sum(ax); ay = epn_wave_sum(ay); az = epn_wave_sum(az);
         const unsigned long long anybad = __ballot(bad != 0);
         if (lane == 0) {
             sh.part[wave][0] = ax; sh.part[wave][1] = ay; sh.part[wave][2] = az;
@@ -184,7 +171,7 @@ __global__ __launch_bounds__(PT) void modelnet_batch_kernel(const float *__restr
                              dz = (double)prow[(size_t)3 * i + 2] - cz;
                 d2 = fmax(d2, dx * dx + dy * dy + dz * dz);
             }
-            d2 = wave_max(d2);
+            d2 = epn_wave_max(d2);
             if (lane == 0) sh.part[wave][0] = d2;
             __syncthreads();
             d2 = 0.0;
@@ -277,16 +264,19 @@ __global__ __launch_bounds__(PT) void modelnet_batch_kernel(const float *__restr
 
 }  // namespace
 
-namespace epn {
-
-int launch_modelnet_batch(const float *points, int m, const int32_t *offsets, int b, const int64_t *ids, int n_sample,
-                          uint64_t seed, int key_bits, int rot_mode, const float *R_in, const float *anchors, int A,
-                          float *pc_out, float *pc_plain, int32_t *idx, float *R, int32_t *R_label, float *R_res, int32_t *status,
-                          hipStream_t st) {
-    EPN_LAUNCH(modelnet_batch_kernel, dim3((unsigned)b), dim3(PT), 0, st, points, m, offsets, ids, n_sample,
+extern "C" int epn_modelnet_batch_f32(const float *points, int m, const int32_t *offsets, int b, const int64_t *ids,
+                                      int n_sample, uint64_t seed, int key_bits, int rot_mode, const float *R_in,
+                                      const float *anchors, int A, float *pc_out, float *pc_plain, int32_t *idx, float *R,
+                                      int32_t *R_label, float *R_res, int32_t *status, epn_stream_t stream) {
+    // every argument is checked before the first HIP runtime call
+    if (b < 0 || m < 0 || n_sample < 1 || n_sample > 8192 || key_bits < 1 || key_bits > 32) return EPN_EINVAL;
+    if (rot_mode < 0 || rot_mode > 2 || (rot_mode == 2 && !R_in)) return EPN_EINVAL;
+    if (anchors && (A < 1 || A > 64)) return EPN_EINVAL;
+    if (b == 0) return 0;
+    if (!offsets || !pc_out || !idx || !R || !status || (m > 0 && !points)) return EPN_EINVAL;
+    if (anchors && (!R_label || !R_res)) return EPN_EINVAL;
+    EPN_LAUNCH(modelnet_batch_kernel, dim3((unsigned)b), dim3(PT), 0, epn_stream(stream), points, m, offsets, ids, n_sample,
                (unsigned long long)seed, key_bits, rot_mode, R_in, anchors, A, pc_out, pc_plain, idx, R, R_label, R_res, status);
     EPN_CHECK_LAUNCH();
     return 0;
 }
-
-}  // namespace epn

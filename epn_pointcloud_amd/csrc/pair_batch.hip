@@ -29,7 +29,6 @@
 #include <cmath>
 
 #include "epn_common.h"
-#include "conv_internal.h"
 #include "patch_sweep.h"
 
 namespace {
@@ -181,18 +180,24 @@ __global__ __launch_bounds__(PT) void fragment_pair_batch_kernel(
 
 }  // namespace
 
-namespace epn {
-
-int launch_fragment_pair_batch(const float *points, int m, const int32_t *offsets, int F, const int32_t *pairs, int B,
-                               const float *corr, int C, const int32_t *corr_offsets, const double *poses, const int64_t *ids,
-                               int n_sample, int npt, float radius, uint64_t seed, int key_bits, int max_degree, int center,
-                               float *src, float *tgt, int32_t *idx, int32_t *counts, int32_t *choice, float *T, float *R_aug,
-                               float *T_aug, int32_t *status, hipStream_t st) {
-    EPN_LAUNCH(fragment_pair_batch_kernel, dim3((unsigned)B * 2u * (unsigned)npt), dim3(PT), 0, st, points, m, offsets, F, pairs,
-               corr, C, corr_offsets, poses, ids, n_sample, npt, radius, (unsigned long long)seed, key_bits, max_degree, center, src,
-               tgt, idx, counts, choice, T, R_aug, T_aug, status);
+// Sizes and scalars first, then B == 0, then pointers -- all before the first HIP runtime call.  The grid is B * 2 * npt
+// workgroups in x.
+extern "C" int epn_fragment_pair_batch_f32(const float *points, int m, const int32_t *offsets, int F, const int32_t *pairs, int B,
+                                           const float *corr, int C, const int32_t *corr_offsets, const double *poses,
+                                           const int64_t *ids, int n_sample, int npt, float radius, uint64_t seed, int key_bits,
+                                           int max_degree, int center, float *src, float *tgt, int32_t *idx, int32_t *counts,
+                                           int32_t *choice, float *T, float *R_aug, float *T_aug, int32_t *status,
+                                           epn_stream_t stream) {
+    if (B < 0 || F < 0 || m < 0 || C < 0 || n_sample < 1 || n_sample > 8192 || npt < 1 || npt > 4096) return EPN_EINVAL;
+    if (key_bits < 1 || key_bits > 32 || max_degree < 0 || max_degree > 360) return EPN_EINVAL;
+    if (!std::isfinite(radius) || !(radius > 0.0f) || (center != 0 && center != 1)) return EPN_EINVAL;
+    if ((long long)B * 2 * npt > 2147483647LL) return EPN_EINVAL;
+    if (B == 0) return 0;
+    if (!offsets || !pairs || !corr_offsets || (m > 0 && !points) || (C > 0 && !corr) || (F > 0 && !poses)) return EPN_EINVAL;
+    if (!src || !tgt || !idx || !counts || !choice || !T || !R_aug || !T_aug || !status) return EPN_EINVAL;
+    EPN_LAUNCH(fragment_pair_batch_kernel, dim3((unsigned)B * 2u * (unsigned)npt), dim3(PT), 0, epn_stream(stream), points, m,
+               offsets, F, pairs, corr, C, corr_offsets, poses, ids, n_sample, npt, radius, (unsigned long long)seed, key_bits,
+               max_degree, center, src, tgt, idx, counts, choice, T, R_aug, T_aug, status);
     EPN_CHECK_LAUNCH();
     return 0;
 }
-
-}  // namespace epn

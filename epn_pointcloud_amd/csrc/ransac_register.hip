@@ -22,7 +22,7 @@
 // (checked) and i_k (a remainder below M); no workgroup waits on another; no atomics: two runs are bitwise equal.
 #include <cmath>
 
-#include "epn_common.h"
+#include "epn_reduce.h"
 #include "philox.h"
 #include "rigid_fit.h"
 #include "scene_tables.h"
@@ -122,9 +122,9 @@ __global__ __launch_bounds__(RT) void ransac_score_kernel(const float *__restric
     if (h < H) hyp_count[(size_t)p * H + h] = ok ? cnt : -1;
 }
 
+// an order of its own (not epn_block_sum's tree): the wave butterfly, then the four wave sums paired as written
 __device__ __forceinline__ double block_sum(double v, double *red) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);        // lanes i and i ^ s add the same two values
+    v = epn_wave_sum(v);
     __syncthreads();                                                   // the previous sum has been read
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -19,7 +19,7 @@
 // from a loop counter, so it lies in 0..A-1 for any wts, NaN included.
 #include <cmath>
 
-#include "epn_common.h"
+#include "epn_reduce.h"
 #include "rotation_math.h"
 
 namespace {
@@ -29,12 +29,6 @@ using epn_rot::rotation_map;
 using epn_rot::so3_project;
 
 constexpr int RW = 64;                   // threads per workgroup = one wave = the most anchors
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x += __shfl_xor(x, s, 64);
-    return x;
-}
 
 __device__ __forceinline__ void load9(const float *__restrict__ p, double m[9]) {
 #pragma unroll
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(RW) void so3_mean_kernel(const float *__restrict__ 
         for (int e = 0; e < 9; ++e) C[e] += w * (double)m[e];
     }
 #pragma unroll
-    for (int e = 0; e < 9; ++e) C[e] = wave_sum(C[e]);
+    for (int e = 0; e < 9; ++e) C[e] = epn_wave_sum(C[e]);
     double Rm[9], mg;
     so3_project(C, Rm, mg);
     if (lane == 0) {
@@ -139,10 +133,10 @@ __global__ __launch_bounds__(RW) void rotation_decode_kernel(const float *__rest
 #pragma unroll
             for (int l = 0; l < 3; ++l) Rp[3 * i + l] = M[3 * i] * Ap[3 * l] + M[3 * i + 1] * Ap[3 * l + 1] + M[3 * i + 2] * Ap[3 * l + 2];
     }
-    const double cf = c / (1e-6 + wave_sum(c));
+    const double cf = c / (1e-6 + epn_wave_sum(c));
     double C[9];
 #pragma unroll
-    for (int e = 0; e < 9; ++e) C[e] = wave_sum(live ? cf * Rp[e] : 0.0);
+    for (int e = 0; e < 9; ++e) C[e] = epn_wave_sum(live ? cf * Rp[e] : 0.0);
     const unsigned long long hit = __ballot(live && label && label[pair * A + a] == p);
     double Rm[9], mg;
     so3_project(C, Rm, mg);

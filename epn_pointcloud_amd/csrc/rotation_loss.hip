@@ -17,7 +17,7 @@
 // directions, and a row whose label lies outside 0..A-1 reads nothing through it.
 #include <cmath>
 
-#include "epn_common.h"
+#include "epn_reduce.h"
 #include "rotation_math.h"
 
 namespace {
@@ -88,19 +88,6 @@ __global__ __launch_bounds__(RW) void rotation_loss_rows_kernel(const float *__r
     for (int e = 0; e < 9; ++e) sel_R[9 * row + e] = (float)R[e];
 }
 
-// sum over the workgroup in a fixed order: every thread's partial into LDS, halved with a barrier per level
-__device__ __forceinline__ double block_sum(double x, double *buf) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    buf[tid] = x;
-    __syncthreads();
-    for (int s = FT / 2; s > 0; s >>= 1) {
-        if (tid < s) buf[tid] += buf[tid + s];
-        __syncthreads();
-    }
-    return buf[0];
-}
-
 __global__ __launch_bounds__(FT) void rotation_loss_finish_kernel(const float *__restrict__ row_ce, const float *__restrict__ row_l2,
                                                                   const int32_t *__restrict__ preds, const int32_t *__restrict__ label,
                                                                   long long rows, double w, float *__restrict__ scalars) {
@@ -111,9 +98,9 @@ __global__ __launch_bounds__(FT) void rotation_loss_finish_kernel(const float *_
         sl += (double)row_l2[i];
         hit += preds[i] == label[i] ? 1.0 : 0.0;
     }
-    sc = block_sum(sc, buf);
-    sl = block_sum(sl, buf);
-    hit = block_sum(hit, buf);
+    sc = epn_block_sum<FT>(sc, buf);
+    sl = epn_block_sum<FT>(sl, buf);
+    hit = epn_block_sum<FT>(hit, buf);
     if (threadIdx.x == 0) {
         const double cls = sc / (double)rows, reg = w * sl / (9.0 * (double)rows);
         scalars[0] = (float)(cls + reg);

@@ -23,7 +23,7 @@
 // interpolation backward) is range-checked on the device before it is used as an address.
 #include <cmath>
 
-#include "epn_common.h"
+#include "epn_reduce.h"
 
 namespace {
 
@@ -129,19 +129,6 @@ __global__ __launch_bounds__(TT) void triplet_rows_kernel(const float *__restric
     row_flags[i] = (pc ? FLAG_POS_CLAMPED : 0) | (ncl ? FLAG_NEG_CLAMPED : 0) | (active ? FLAG_HINGE_ACTIVE : 0);
 }
 
-// sum over the workgroup in a fixed order: every thread's partial into LDS, halved with a barrier per level
-__device__ __forceinline__ double block_sum(double x, double *buf) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    buf[tid] = x;
-    __syncthreads();
-    for (int s = TT / 2; s > 0; s >>= 1) {
-        if (tid < s) buf[tid] += buf[tid + s];
-        __syncthreads();
-    }
-    return buf[0];
-}
-
 __global__ __launch_bounds__(TT) void triplet_finish_kernel(const float *__restrict__ d_pos, const float *__restrict__ d_neg,
                                                             const float *__restrict__ row_loss, const int32_t *__restrict__ nn_idx,
                                                             int N, float *__restrict__ scalars) {
@@ -153,10 +140,10 @@ __global__ __launch_bounds__(TT) void triplet_finish_kernel(const float *__restr
         sn += (double)d_neg[i];
         hit += nn_idx[i] == i ? 1.0 : 0.0;
     }
-    sl = block_sum(sl, buf);
-    sp = block_sum(sp, buf);
-    sn = block_sum(sn, buf);
-    hit = block_sum(hit, buf);
+    sl = epn_block_sum<TT>(sl, buf);
+    sp = epn_block_sum<TT>(sp, buf);
+    sn = epn_block_sum<TT>(sn, buf);
+    hit = epn_block_sum<TT>(hit, buf);
     if (threadIdx.x == 0) {
         scalars[0] = (float)(sl / N);
         scalars[1] = (float)(hit / N);

@@ -1194,7 +1194,7 @@ typedef struct epn_gemm_nt_problem {
      * take: the per-channel statistics pass of a following BatchNorm / InstanceNorm (base_so3conv.py:196-204) without
      * reading C again. */
     float *col_stats;
-    /* Optional (NULL: off; library 0.4): device scalar the kernel RAISES to max|C| (values as stored; non-finite ones left
+    /* Optional (NULL: off; library 0.5): device scalar the kernel RAISES to max|C| (values as stored; non-finite ones left
      * out) from its accumulators -- zero it before the call.  What epn_inter_ungroup_cloud_* takes as dg_amax when C is the
      * gradient of the grouped features. */
     float *c_amax;
@@ -1304,7 +1304,7 @@ int epn_inter_bwd_data_f16x2_f32(const epn_inter_desc *d, const float *grad_out_
  * the representable range: such a workgroup writes NaN to its rows and bumps a sticky device counter
  * (epn_inter_ungroup_cloud_range_count; reset != 0 clears it), as does a non-finite grad_grouped.
  * Shapes (epn_..._ok): the MFMA grouping's (cin % 16 == 0, ks % 4 == 0, ks <= 32, nn <= 64), p2 <= 4096, and p1 small enough
- * for (p1 + 4) * 16 * 8 bytes of accumulators (p1 <= 1275). */
+ * for (p1 + 4) * 16 * 8 + 16 bytes of accumulators to fit the 160 KB of a CU's LDS (p1 <= 1275). */
 int epn_inter_ungroup_cloud_ok(const epn_inter_desc *d);
 size_t epn_inter_ungroup_cloud_workspace_bytes(const epn_inter_desc *d);
 int epn_inter_ungroup_cloud_f32(const epn_inter_desc *d, const float *grad_grouped, const float *dg_amax, float *grad_feats_cl,
