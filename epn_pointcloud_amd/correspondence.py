@@ -23,6 +23,7 @@ from . import _lib
 from .data import _tensor
 
 KeypointPairs = collections.namedtuple("KeypointPairs", ["rows", "src_centroid_row", "d2"])
+PointNormals = collections.namedtuple("PointNormals", ["normals", "eig", "count", "flags", "moments", "neighbors"])
 
 
 def _grouping():
@@ -69,6 +70,26 @@ class PointGrid:
             raise ValueError(f"radius must not exceed the grid's max_radius {self.max_radius}, got {radius}")
         return _grouping().point_grid_nn(self._workspace, self.n, queries, radius, exclude_row=exclude_self, count=count)
 
+    def normals(self, queries=None, radius=None, max_nn=30, view=None, return_moments=False, return_neighbors=False):
+        """queries f32 [m,3] (None: the grid's own points) -> PointNormals(normals f32 [m,3], eig f32 [m,3], count int32 [m],
+        flags int32 [m], moments int64 [m,9], neighbors int32 [m,max_nn]), the last two None unless asked for: the plane
+        through every query's neighbourhood -- the grid's points within radius, cut to the max_nn nearest (the lowest row on a
+        distance tie; 0 = no limit) -- as
+        include/epn_so3conv.h states it (epn_point_normals_f32): the unit normal, the covariance's eigenvalues in ascending
+        order (in the cloud's squared units), the size of the in-radius set, and flags bit 0 (fewer than three neighbours: the
+        normal is (0, 0, 1)), bit 1 (a non-finite query) and bit 2 (the two smallest eigenvalues coincide: a line or a point,
+        the direction is arbitrary).  view (three floats or a device tensor: a camera position, the fragment's own origin for
+        a fused fragment) turns every normal towards it; without it the normal's largest component is positive.  radius
+        defaults to the grid's max_radius."""
+        radius = self.max_radius if radius is None else radius
+        if not float(radius) <= self.max_radius:
+            raise ValueError(f"radius must not exceed the grid's max_radius {self.max_radius}, got {radius}")
+        if view is not None and not isinstance(view, torch.Tensor):
+            view = torch.as_tensor(view, dtype=torch.float32).reshape(-1).to(self.points.device)
+        return PointNormals(*_grouping().point_normals(
+            self._workspace, self.n, self.points if queries is None else queries, radius, max_nn=max_nn,
+            self_rows=queries is None, view=view, return_moments=return_moments, return_neighbors=return_neighbors))
+
 
 def _grid(cloud, name, max_radius):
     """cloud: a PointGrid (its max_radius must cover max_radius) or a tensor to build one from."""
@@ -77,6 +98,21 @@ def _grid(cloud, name, max_radius):
             raise ValueError(f"{name}: the grid was built for radii up to {cloud.max_radius}, {max_radius} is needed")
         return cloud
     return PointGrid(_tensor(cloud, name, (None, 3), torch.float32), max_radius)
+
+
+def estimate_normals(points_or_grid, radius, max_nn=30, view=None):
+    """(points f32 [n,3] or their PointGrid, built with max_radius >= radius) -> PointNormals of the cloud's own points: the
+    device form of open3d's pc.estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) followed, with a view, by
+    orient_normals_towards_camera_location(view) (the reference: SPConvNets/datasets/preprocess/run_fusion.py:48).  The
+    correspondence with open3d is argued from its algorithm; it has not been run against open3d."""
+    return _grid(points_or_grid, "points", float(radius)).normals(None, radius, max_nn=max_nn, view=view)
+
+
+def orient_patches(patches, normals):
+    """(patches f32 [k,n_sample,3], normals f32 [k,3]) -> f32 [k,n_sample,3]: every patch in the frame of its keypoint's normal,
+    the reference's transform_with_normals (SPConvNets/datasets/match_3dmatch.py:141-152) as include/epn_so3conv.h states it
+    (epn_orient_patches_f32).  A zero patch stays zero."""
+    return _grouping().orient_patches(patches, normals)[0]
 
 
 def fragment_overlap(src, tgt, margin=0.075, ratio=0.3):

@@ -18,6 +18,33 @@ __device__ __forceinline__ double epn_wave_max(double x) {
     return x;
 }
 
+// The same butterfly on integers (int, long long, their unsigned forms): sum, minimum and maximum over the wave in every lane.
+// Integer addition is exact, so these do not depend on the order at all.
+template <typename I>
+__device__ __forceinline__ I epn_wave_isum(I x) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) x += __shfl_xor(x, s, 64);
+    return x;
+}
+template <typename I>
+__device__ __forceinline__ I epn_wave_imin(I x) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const I o = __shfl_xor(x, s, 64);
+        x = o < x ? o : x;
+    }
+    return x;
+}
+template <typename I>
+__device__ __forceinline__ I epn_wave_imax(I x) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const I o = __shfl_xor(x, s, 64);
+        x = o > x ? o : x;
+    }
+    return x;
+}
+
 // Sum over a workgroup of T threads (one dimension, T a power of two) through buf[T] in LDS: every thread stores its value, then
 // level s = T / 2, T / 4, .. 1 adds buf[tid + s] into buf[tid] for tid < s, with a barrier per level; the result is buf[0], the
 // same bits in every thread.  The barrier in front of the store lets the same buf serve one sum after another.

@@ -28,45 +28,14 @@
 #include <mutex>
 #include <unordered_map>
 
-#include "cell_hash.h"
+#include "point_grid.h"
 
-namespace {
-
-using namespace epn_cells;
-
-constexpr double MIN_RADIUS = 0x1p-60;   // below it the fp32 products of admissible differences underflow (the header's argument)
-constexpr int QW = 4;                    // queries (waves) per workgroup
-
-struct Slot {                            // 16 bytes: one cell
-    unsigned long long key;
-    int count;                           // its points
-    int cursor;                          // offsets: the start of its run; after scatter: the end
-};
-
-struct Layout {
-    int log2cap;
-    size_t cap, records, slots, pslot, tsum, bytes;   // byte offsets of the records, the table, the points' slots, the tile sums
-};
-
-Layout layout(int64_t n) {
-    Layout L;
-    L.log2cap = log2_capacity(n);
-    L.cap = (size_t)1 << L.log2cap;
-    L.records = sizeof(Head);
-    L.slots = L.records + (size_t)n * sizeof(int4);
-    L.pslot = L.slots + L.cap * sizeof(Slot);
-    L.tsum = L.pslot + (size_t)n * sizeof(int);
-    L.bytes = L.tsum + (size_t)epn_cdiv((long long)L.cap, VT) * sizeof(int);
-    return L;
-}
+namespace epn_grid {
 
 // What the query's argument checks need of the build, kept on the host per workspace address (the workspace itself is device
 // memory, and a refusal is decided before any HIP runtime call).  A build replaces its address' entry.  The table is emptied
 // when it reaches MAX_GRIDS addresses: queries on the grids built before that are then refused until they are built again.
-struct Built {
-    int64_t n;
-    double max_radius;
-};
+namespace {
 constexpr size_t MAX_GRIDS = 1 << 16;
 std::mutex g_mutex;
 std::unordered_map<const void *, Built> g_built;
@@ -76,6 +45,7 @@ void remember(const void *workspace, int64_t n, double max_radius) {
     if (g_built.size() >= MAX_GRIDS && !g_built.count(workspace)) g_built.clear();
     g_built[workspace] = Built{n, max_radius};
 }
+}  // namespace
 
 bool recall(const void *workspace, Built &b) {
     std::lock_guard<std::mutex> lock(g_mutex);
@@ -85,7 +55,13 @@ bool recall(const void *workspace, Built &b) {
     return true;
 }
 
-double cell_edge(double max_radius) { return max_radius * (1.0 + 0x1p-10); }
+}  // namespace epn_grid
+
+namespace {
+
+using namespace epn_grid;
+
+constexpr double MIN_RADIUS = 0x1p-60;   // below it the fp32 products of admissible differences underflow (the header's argument)
 
 __device__ __forceinline__ bool takes_part(const float *__restrict__ ref, const uint8_t *__restrict__ valid, int i, float &x,
                                            float &y, float &z) {
@@ -180,19 +156,6 @@ __global__ void grid_zero_hits_kernel(int32_t *hits) {
     if (threadIdx.x == 0) *hits = 0;
 }
 
-constexpr unsigned long long NONE = ~0ull;
-
-// (dx*dx + dy*dy) + dz*dz, every operation rounded on its own.  Plain operators under "fp contract(off)": the pragma governs the
-// operations written in its scope, and the __f*_rn intrinsics are inline functions of the HIP headers, compiled outside it, whose
-// products this compiler fuses into fma.
-__device__ __forceinline__ float dist2(float px, float py, float pz, float qx, float qy, float qz) {
-#pragma clang fp contract(off)
-    const float dx = px - qx, dy = py - qy, dz = pz - qz;
-    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    const float xy = xx + yy;
-    return xy + zz;
-}
-
 // n == 0 (an empty grid) reads nothing of head, slots and records.
 __global__ __launch_bounds__(QW * 64) void grid_nn_kernel(const Head *__restrict__ head, const Slot *__restrict__ slots,
                                                           const int4 *__restrict__ records, int n, int log2cap, double edge,
@@ -206,44 +169,15 @@ __global__ __launch_bounds__(QW * 64) void grid_nn_kernel(const Head *__restrict
     if (q < m && n > 0) {
         const float qx = qry[3 * (size_t)q], qy = qry[3 * (size_t)q + 1], qz = qry[3 * (size_t)q + 2];
         if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
-            // the cell of lane l < 27: the query's, moved by (l % 3 - 1, l / 3 % 3 - 1, l / 9 - 1).  An index outside [0, 2^21)
-            // on an axis (far queries included: the comparison is made in fp64, before any conversion) holds no point.
-            const int c = lane < 27 ? lane : 13;
-            const double ix = cell_axis(qx, head->lo[0], edge) + (double)(c % 3 - 1);
-            const double iy = cell_axis(qy, head->lo[1], edge) + (double)(c / 3 % 3 - 1);
-            const double iz = cell_axis(qz, head->lo[2], edge) + (double)(c / 9 - 1);
-            int start = 0, count = 0;
-            if (lane < 27 && ix >= 0.0 && ix < INDEX_END && iy >= 0.0 && iy < INDEX_END && iz >= 0.0 && iz < INDEX_END) {
-                const int s = find_slot(slots, cell_key(ix, iy, iz), log2cap);
-                if (s >= 0) {
-                    const int end = min(max(slots[s].cursor, 0), n);
-                    count = min(max(slots[s].count, 0), end);
-                    start = end - count;
-                }
-            }
-            int incl = count;                              // lanes 27..63 add nothing: five steps cover lanes 0..31
-#pragma unroll
-            for (int s = 1; s < 32; s <<= 1) {
-                const int up = __shfl_up(incl, s, 64);
-                if (lane >= s) incl += up;
-            }
-            const int first = incl - count;                // the number of this lane's first candidate
-            const int total = __shfl(incl, 31, 64);
-            for (int base = 0; base < total; base += 64) { // every lane runs every pass: the shuffles read all of them
-                const int t = base + lane;
-                int cell = 0;                              // the last cell whose first candidate is <= t: t is one of its own
-#pragma unroll
-                for (int step = 16; step > 0; step >>= 1) {
-                    const int f = __shfl(first, cell + step, 64);
-                    if (cell + step < 27 && f <= t) cell += step;
-                }
-                const int at = __shfl(start, cell, 64) + (t - __shfl(first, cell, 64));
-                if (t < total && at >= 0 && at < n) {
+            const Cells cells = find_cells(head, slots, n, log2cap, edge, qx, qy, qz, lane);
+            for (int base = 0; base < cells.total; base += 64) {   // every lane runs every pass: the shuffles read all of them
+                const int at = record_of(cells, base + lane, n);
+                if (at >= 0) {
                     const int4 p = records[at];
                     const int row = p.w;
                     const float d2 = dist2(__int_as_float(p.x), __int_as_float(p.y), __int_as_float(p.z), qx, qy, qz);
                     if (d2 <= r2 && !(exclude_row && row == q)) {
-                        const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)row;
+                        const unsigned long long k = member_key(d2, row);
                         best = k < best ? k : best;
                     }
                 }

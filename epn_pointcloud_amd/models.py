@@ -238,7 +238,7 @@ class InvSO3ConvModel(_SO3ConvModel):
     search_radius = None        # build_inv records the configuration's patch radius and size here: plain attributes, not
     input_num = None            # buffers or parameters (the state_dict is the reference's, key for key)
 
-    def describe(self, pc, keypoints, *, radius=None, batch=64, seed=0, voxel_size=None):
+    def describe(self, pc, keypoints, *, radius=None, batch=64, seed=0, voxel_size=None, normals=None):
         """(pc f[n,3], keypoints f[k,3] or integer rows [k]) -> (descriptors f32 [k, c_out], valid bool [k]): the
         descriptors of a fragment's keypoints.  The patches are extracted once on the device (vgtk.pc.radius_patches:
         radius `radius` or the model's search_radius, input_num points each) and go through forward() in batches of `batch`
@@ -247,7 +247,10 @@ class InvSO3ConvModel(_SO3ConvModel):
         last, partial batch is padded with zero patches whose rows are dropped.
         voxel_size (a float, or "reference": vgtk.pc.reference_voxel_size(input_num)) downsamples the fragment to its voxel
         centroids first (vgtk.pc.voxel_down_sample) and extracts the patches from those, as the reference's loaders do; integer
-        keypoints are rows of the ORIGINAL pc, resolved to coordinates before the downsampling.  None: the fragment as given."""
+        keypoints are rows of the ORIGINAL pc, resolved to coordinates before the downsampling.  None: the fragment as given.
+        normals (the reference's --normals, opt.model.normals): f32 [k,3], the fragment's normals at the keypoints, or, with
+        integer keypoints, f32 [n,3], the normals of the ORIGINAL pc (vgtk.pc.estimate_normals), gathered at those rows; every
+        patch is turned into its keypoint's normal frame before the network sees it (vgtk.pc.orient_patches).  None: no frame."""
         from .vgtk import pc as pctk
         if self.training:
             raise RuntimeError("describe() needs the model in eval() mode: call model.eval() first")
@@ -258,6 +261,15 @@ class InvSO3ConvModel(_SO3ConvModel):
         batch = int(batch)
         if batch < 1:
             raise ValueError(f"batch must be >= 1, got {batch}")
+        if normals is not None:
+            if not isinstance(normals, torch.Tensor) or normals.dim() != 2 or normals.shape[1] != 3:
+                raise ValueError("normals must be a [k,3] tensor (or [n,3] with integer keypoints), got "
+                                 f"{tuple(normals.shape) if isinstance(normals, torch.Tensor) else type(normals).__name__}")
+            if not keypoints.is_floating_point() and keypoints.dim() == 1 and normals.shape[0] == pc.shape[0]:
+                normals = normals.index_select(0, keypoints.long())
+            if normals.shape[0] != keypoints.shape[0]:
+                raise ValueError(f"normals must hold one row per keypoint ({keypoints.shape[0]}) or, with integer keypoints, "
+                                 f"per point of pc ({pc.shape[0]}), got {normals.shape[0]}")
         with torch.no_grad():
             if voxel_size is not None:
                 if not keypoints.is_floating_point():
@@ -266,7 +278,7 @@ class InvSO3ConvModel(_SO3ConvModel):
                     keypoints = pc.index_select(0, keypoints.long())
                 size = pctk.reference_voxel_size(self.input_num) if voxel_size == "reference" else float(voxel_size)
                 pc = pctk.voxel_down_sample(pc, size)[0]
-            patches, _, counts = pctk.radius_patches(pc, keypoints, radius, self.input_num, seed=seed)
+            patches, _, counts = pctk.radius_patches(pc, keypoints, radius, self.input_num, seed=seed, normals=normals)
             valid = counts > 1
             rows = torch.nonzero(valid).flatten()
             desc = None

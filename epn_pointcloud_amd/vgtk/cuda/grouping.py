@@ -172,6 +172,77 @@ def point_grid_nn(workspace, n, queries, radius, exclude_row=False, count=False)
     return (nn_idx, nn_d2, hits) if count else (nn_idx, nn_d2)
 
 
+MAX_NORMAL_NN = 1024
+
+
+def point_normals(workspace, n, queries, radius, max_nn=30, self_rows=False, view=None, return_moments=False,
+                  return_neighbors=False):
+    """(workspace from point_grid_build of n points, queries f[m,3], float radius <= the build's max_radius, int max_nn with
+    0 = no limit, view f[3] on the device or None) -> (normals f[m,3], eig f[m,3], count int32 [m], flags int32 [m], moments
+    int64 [m,9] or None, neighbors int32 [m,max_nn] or None): the plane fitted to every query's neighbourhood in the grid
+    (epn_point_normals_f32, include/epn_so3conv.h; no counterpart among the reference's extensions -- it replaces open3d's
+    estimate_normals of SPConvNets/datasets/preprocess/run_fusion.py:48).  self_rows states that the queries are the grid's
+    own points."""
+    from ...data import _tensor
+    lib = _lib.get_lib()
+    queries = _tensor(queries, "queries", (None, 3), torch.float32)
+    workspace = _tensor(workspace, "workspace", (None,), torch.int64)
+    if view is not None:
+        view = _tensor(view, "view", (3,), torch.float32)
+    n, m, r, nn = int(n), queries.shape[0], float(radius), int(max_nn)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"radius must be finite and > 0, got {radius}")
+    if not 0 <= nn <= MAX_NORMAL_NN:
+        raise ValueError(f"max_nn must be in 0..{MAX_NORMAL_NN} (0 = no limit), got {max_nn}")
+    if return_neighbors and nn == 0:
+        raise ValueError("return_neighbors needs max_nn >= 1: the rows of an unlimited neighbourhood have no fixed width")
+    if m > MAX_GRID_POINTS:
+        raise ValueError(f"a call takes at most 2^22 queries, got {m}")
+    if self_rows and m != n:
+        raise ValueError(f"self_rows needs the grid's own {n} points as queries, got {m}")
+    _lib.same_device(workspace, queries, view)
+    f32, i32 = dict(dtype=torch.float32, device=queries.device), dict(dtype=torch.int32, device=queries.device)
+    normals, eig = torch.empty((m, 3), **f32), torch.empty((m, 3), **f32)
+    count, flags = torch.empty((m,), **i32), torch.empty((m,), **i32)
+    moments = torch.empty((m, 9), dtype=torch.int64, device=queries.device) if return_moments else None
+    neighbors = torch.empty((m, nn), **i32) if return_neighbors else None
+    _lib.check(lib.epn_point_normals_f32(ctypes.c_void_p(workspace.data_ptr()), n, _lib.dev_ptr(queries, "queries"), m, r, nn,
+                                         int(bool(self_rows)), _lib.dev_ptr(view, "view"), _lib.dev_ptr(normals, "normals"),
+                                         _lib.dev_ptr(eig, "eig"), _lib.dev_ptr(count, "count", torch.int32),
+                                         _lib.dev_ptr(flags, "flags", torch.int32),
+                                         _lib.dev_ptr(moments, "moments", torch.int64),
+                                         _lib.dev_ptr(neighbors, "neighbors", torch.int32), _lib.stream_of(queries)),
+               "point_normals")
+    return normals, eig, count, flags, moments, neighbors
+
+
+def orient_patches(patches, normals, out=None):
+    """(patches f[k,n_sample,3], normals f[k,3]) -> (out f[k,n_sample,3], axis f[k,3,3]): every patch in the frame of its normal,
+    out = patch @ axis (epn_orient_patches_f32, include/epn_so3conv.h; no counterpart among the reference's extensions -- it
+    replaces transform_with_normals of SPConvNets/datasets/match_3dmatch.py:141-152).  out may be `patches` itself."""
+    from ...data import _tensor
+    lib = _lib.get_lib()
+    patches = _tensor(patches, "patches", (None, None, 3), torch.float32)
+    k, ns = patches.shape[0], patches.shape[1]
+    normals = _tensor(normals, "normals", (k, 3), torch.float32)
+    if not 1 <= ns <= 8192:
+        raise ValueError(f"n_sample must be in 1..8192, got {ns}")
+    if k > MAX_GRID_POINTS:
+        raise ValueError(f"a call takes at most 2^22 patches, got {k}")
+    if out is None:
+        out = torch.empty_like(patches)
+    else:
+        if isinstance(out, torch.Tensor) and not out.is_contiguous():
+            raise RuntimeError("out must be contiguous: the result is written into it")
+        out = _tensor(out, "out", (k, ns, 3), torch.float32)
+    _lib.same_device(patches, normals, out)
+    axis = torch.empty((k, 3, 3), dtype=torch.float32, device=patches.device)
+    _lib.check(lib.epn_orient_patches_f32(_lib.dev_ptr(patches, "patches"), _lib.dev_ptr(normals, "normals"), k, ns,
+                                          _lib.dev_ptr(axis, "axis"), _lib.dev_ptr(out, "out"), _lib.stream_of(patches)),
+               "orient_patches")
+    return out, axis
+
+
 def _scene_tables(frag_off, pairs, device):
     """Host copies (contiguous numpy: what the library's argument checks read) and device copies (what its kernels read) of a
     scene's tables, with out_off / tgt_off computed from them (include/epn_so3conv.h, "Scene tables")."""

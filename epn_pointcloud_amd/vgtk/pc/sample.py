@@ -17,28 +17,36 @@ def ball_query_index(query_points, support_points, radius, n_sample):
     return cuda_nn.ball_query(query_points, support_points, radius, n_sample)
 
 
-def radius_patches(pc, keypoints, radius, n_sample, *, seed=0, center=False, scale=1.0, rows_per_call=None):
+def radius_patches(pc, keypoints, radius, n_sample, *, seed=0, center=False, scale=1.0, rows_per_call=None,
+                   normals=None):
     """[n,3] x keypoints -> (patches f[k,n_sample,3], idx int32 [k,n_sample], counts int32 [k]): around every keypoint,
     the points of the fragment within `radius`, resampled to n_sample.  The device form of what the reference does on the
     host with a KD-tree and np.random.choice (match_3dmatch.py:154-177, sample.py:16-36), in the library's deterministic
     statement of it (include/epn_so3conv.h: epn_radius_patches_f32): rows with counts <= 1 are idx -1 / zero patches.
     keypoints: float [k,3] coordinates, or an integer [k] tensor of rows of pc (what the reference passes).
-    rows_per_call splits the keypoints over several launches; the result is the same by specification."""
+    rows_per_call splits the keypoints over several launches; the result is the same by specification.
+    normals f32 [k,3], the fragment's normals at the keypoints: every patch is turned into its keypoint's normal frame
+    (orient_patches, in place on the result), what the reference's loader does with return_normals (match_3dmatch.py:136-137)."""
     if not keypoints.is_floating_point():
         if keypoints.dim() != 1:
             raise ValueError(f"integer keypoints must be [k] rows of pc, got {tuple(keypoints.shape)}")
         keypoints = pc.index_select(0, keypoints.long())
     keypoints = keypoints.contiguous()
     k = keypoints.shape[0]
+    if normals is not None and (not isinstance(normals, torch.Tensor) or tuple(normals.shape) != (k, 3)):
+        raise ValueError(f"normals must be a [k,3] = [{k},3] tensor, one normal per keypoint, got "
+                         f"{tuple(normals.shape) if isinstance(normals, torch.Tensor) else type(normals).__name__}")
     step = k if rows_per_call is None else int(rows_per_call)
     if rows_per_call is not None and step < 1:
         raise ValueError(f"rows_per_call must be >= 1, got {rows_per_call}")
     if step >= k:
         idx, counts, patches = cuda_nn.radius_patches(pc, keypoints, radius, n_sample, seed=seed, center=center, scale=scale)
-        return patches, idx, counts
-    parts = [cuda_nn.radius_patches(pc, keypoints[r0:r0 + step], radius, n_sample, seed=seed, kpt_row0=r0, center=center,
-                                    scale=scale) for r0 in range(0, k, step)]
-    idx, counts, patches = (torch.cat([p[i] for p in parts]) for i in range(3))
+    else:
+        parts = [cuda_nn.radius_patches(pc, keypoints[r0:r0 + step], radius, n_sample, seed=seed, kpt_row0=r0, center=center,
+                                        scale=scale) for r0 in range(0, k, step)]
+        idx, counts, patches = (torch.cat([p[i] for p in parts]) for i in range(3))
+    if normals is not None:
+        cuda_nn.orient_patches(patches, normals, out=patches)
     return patches, idx, counts
 
 

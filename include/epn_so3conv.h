@@ -413,6 +413,59 @@ int epn_point_grid_build_f32(const float *ref, int64_t n, const uint8_t *ref_val
 int epn_point_grid_nn_f32(const void *workspace, int64_t n, const float *qry, int64_t m, double radius, int exclude_row,
                           int32_t *nn_idx, float *nn_d2, int32_t *hits, epn_stream_t stream);
 
+/* Surface normals and patch frames (csrc/point_normals.hip, csrc/plane_fit.h): the reference's --normals switch
+ * (opt.model.normals).  It estimates a fragment's normals once on the host with open3d (preprocess/run_fusion.py:48,
+ * pc.estimate_normals()), reads them at the keypoints (match_3dmatch.py:117-120) and turns every patch into its keypoint's normal
+ * frame (transform_with_normals, :141-152).  The contract fixes the result, not the schedule.
+ *
+ * epn_point_normals_f32: the grid of a build (workspace address and n, as epn_point_grid_nn_f32 takes them), qry f32[m,3], radius,
+ *   max_nn, view f32[3] on the device or NULL -> normals f32[m,3], eig f32[m,3], count i32[m], flags i32[m], and, each NULL-able,
+ *   moments i64[m,9] and nbr_idx i32[m,max_nn].
+ *   in-radius set   the grid's points with d2 <= r2, d2 and r2 exactly as in epn_point_grid_nn_f32 (individually rounded fp32, no
+ *                   fma, inclusive, r2 = (float)(radius * radius) from the fp64 product).  The query's own point, when it is in
+ *                   the grid, is a member like any other.  count = the size of this set, not clamped.
+ *   neighbourhood   max_nn > 0 and count > max_nn: the max_nn members smallest in the 64-bit key d2 bits << 32 | row, which is
+ *                   open3d's KDTreeSearchParamHybrid made deterministic (the lowest row on a distance tie).  Otherwise the whole
+ *                   set (KDTreeSearchParamRadius).  used = min(count, max_nn) (= count with max_nn == 0).  nbr_idx holds the
+ *                   neighbourhood's rows in ascending key order, -1 beyond used.
+ *   moments         for a neighbour p of the query q, per axis t = ((double)p - (double)q) / radius: two fp64 operations, each
+ *                   rounded once.  S_i = sum rint(t_i 2^40), M_ij = sum rint((t_i t_j) 2^40) for ij = xx, xy, xz, yy, yz, zz, the
+ *                   product rounded once (no fma) before the exact scaling; all sums int64.  |t| < 1 + 2^-20 and n <= 2^22 keep
+ *                   every sum below 2^63.  moments = {S_x, S_y, S_z, M_xx, M_xy, M_xz, M_yy, M_yz, M_zz}.  Integer sums do not
+ *                   depend on their order, and the order of the records inside a cell is free: hence the fixed point.
+ *   plane fit       in fp64, every operation rounded on its own: mean_i = (S_i / 2^40) / used, C_ij = (M_ij / 2^40) / used -
+ *                   mean_i mean_j; a cyclic Jacobi (10 sweeps over (0,1), (0,2), (1,2), the rotations of the SO(3) projection)
+ *                   gives the eigenvalues, sorted ascending with the lowest index first on a tie; eig = (float)(lambda * (radius *
+ *                   radius)); the normal is the eigenvector of lambda0, normalised in fp64.
+ *   sign            with view: flipped so that (n0 (v0 - q0) + n1 (v1 - q1)) + n2 (v2 - q2) >= 0 in fp64 (open3d's
+ *                   orient_normals_towards_camera_location; a fused fragment's own origin is a camera position).  Without: the
+ *                   component of largest magnitude is positive, the lowest axis on a tie.  Then rounded once to fp32.
+ *   flags           bit 0: used < 3; the normal is (0, 0, 1), whatever the view, and eig is zero (open3d's fallback).  bit 1: a
+ *                   non-finite query coordinate; it reads no cell, count = 0 (so bit 0 is set as well).  bit 2: lambda1 -
+ *                   lambda0 <= 2^-40 in the units of C: the direction is not determined; the computed one is still returned.
+ *                   Nothing asserts, and no query affects another.
+ *   self_rows       1 states that the queries are the grid's own points (m == n is required); nothing is skipped.
+ *   One launch: one wave per query, four per workgroup; count, a bisection on the key for the max_nn cut (only where count >
+ *   max_nn), the moment sweep with an integer xor tree across the wave, then threads 0..3 of the workgroup finish one query each.
+ *   No floating-point atomics, no allocation, no host synchronisation: bitwise repeatable and graph-capturable.
+ *   0 <= n, m <= 2^22, radius finite, 0 < radius <= max_radius of the build, max_nn in 0..1024, no nbr_idx with max_nn == 0,
+ *   self_rows 0 or 1 and m == n with 1, a workspace address and n that a build has been called with, and qry, normals, eig, count,
+ *   flags when m > 0: EPN_EINVAL otherwise, decided before any HIP runtime call.  m == 0 succeeds and launches nothing.
+ *
+ * epn_orient_patches_f32: patches f32[k,n_sample,3], normals f32[k,3] -> axis f32[k,3,3], out f32[k,n_sample,3]; out may be
+ *   patches.  u(v) = v / (|v| + 1e-5) with |v| = sqrt((v0 v0 + v1 v1) + v2 v2), all in fp64, every operation rounded on its own:
+ *   z = u(n), x = u(up cross z) with up = (0, -1, 0), y = u(z cross x), the cross product (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 -
+ *   a1 b0); axis has x, y, z as its COLUMNS, rounded once to fp32.  With the normal parallel to up the frame's x and y are zero,
+ *   as upstream; nothing becomes NaN.  out = patch @ axis: component j = ((p0 a0j + p1 a1j) + p2 a2j) in fp64 from the ROUNDED
+ *   axis, rounded once (the convention of epn_fragment_pair_batch_f32's rotation); zero rows stay zero.  One workgroup per patch,
+ *   one launch.  0 <= k <= 2^22, n_sample in 1..8192, no NULL pointer when k > 0: EPN_EINVAL otherwise, decided before any HIP
+ *   runtime call.  k == 0 succeeds and launches nothing. */
+int epn_point_normals_f32(const void *workspace, int64_t n, const float *qry, int64_t m, double radius, int max_nn, int self_rows,
+                          const float *view, float *normals, float *eig, int32_t *count, int32_t *flags, int64_t *moments,
+                          int32_t *nbr_idx, epn_stream_t stream);
+int epn_orient_patches_f32(const float *patches, const float *normals, int64_t k, int n_sample, float *axis, float *out,
+                           epn_stream_t stream);
+
 /* Rotation estimation: what turns RegSO3ConvModel's head output into a rotation, the labels a training step needs and the
  * angular error the reference reports.  All tensors are contiguous device memory, float or int32; anchors
  * f32[A,3,3], 1 <= A <= 64.  Arithmetic is fp64 on the fp32 inputs and every output is rounded once to fp32.  One wave per
