@@ -1467,7 +1467,7 @@ extern "C" int epn_conv1x1_c1_bwd_weight_ws_f32(const float *x, const float *gra
     EPN_LAUNCH(epn::c1_outer_bwd_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, x,
                        reinterpret_cast<const f32x4 *>(grad_y), static_cast<float *>(workspace), rows, cout / 4, rpb);
     EPN_CHECK_LAUNCH();
-    EPN_LAUNCH(epn::c1_outer_bwd_finish_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, st,
+    EPN_LAUNCH_AUX(epn::c1_outer_bwd_finish_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, st,
                        static_cast<const float *>(workspace), grad_w, (int)nb, cout);
     EPN_CHECK_LAUNCH();
     return 0;

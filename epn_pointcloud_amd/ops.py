@@ -2078,7 +2078,9 @@ class GatherRowsFn(torch.autograd.Function):
 
 
 def gather_rows(feats, sample_idx):
-    """Rows of a [b,c,p,a] tensor selected along p; needs a*c*elem_size % 16 == 0 (else torch.gather)."""
+    """Rows of a [b,c,p,a] tensor selected along p; needs a*c*elem_size % 16 == 0 (else torch.gather).  More than 8192
+    selected rows per cloud also take torch.gather: the gradient of a repeated index is then torch's sum, which for bf16 rounds
+    after every add and in no fixed order, where the kernel sums in fp32 in ascending row order and rounds once."""
     if feats.is_cuda and (feats.shape[1] * feats.shape[3] * feats.element_size()) % 16 == 0 and \
             feats.dtype in FEATURE_DTYPES and sample_idx.shape[1] <= 8192:
         return GatherRowsFn.apply(feats, sample_idx)
@@ -2164,6 +2166,12 @@ class Conv1x1C1Fn(torch.autograd.Function):
         return gx, gw
 
 
+def conv1x1_c1_takes(cout):
+    """Widths the outer-product kernels of a single input channel take: what epn_conv1x1_c1_f32 AND both of its weight-gradient
+    entries accept (whole 16-byte groups, at most 1024, a whole number of channel groups per 256-thread block)."""
+    return 4 <= cout <= 1024 and cout % 4 == 0 and 256 % (cout // 4) == 0
+
+
 def conv1x1(x, weight, bias=None, col_stats=False, x_amax=None):
     """nn.Conv2d(cin, cout, 1) on a [b,c,p,a] tensor, channels-last in and out with no layout copy: one NT GEMM
     [cols, cin] x [cout, cin]^T on the zero-copy 2-D view (fp32 master weight, cast per call for bf16 features).
@@ -2196,7 +2204,7 @@ def conv1x1(x, weight, bias=None, col_stats=False, x_amax=None):
         y = IntraSO3ConvFn.apply(cast_feats(x, torch.float32), weight.reshape(cout, cin),
                                  _identity_index(x.shape[3], x.device))
         y = cast_feats(y, x.dtype)
-    elif x.is_cuda and cin == 1 and cout % 4 == 0 and 256 % (cout // 4) == 0 and cout <= 1024:
+    elif x.is_cuda and cin == 1 and conv1x1_c1_takes(cout):
         # single input channel (the occupancy feature of the first block): an outer product, written channels-last
         b, _, p, a = x.shape
         y2d = Conv1x1C1Fn.apply(to_cl(x).float().reshape(-1), weight.reshape(cout).float())

@@ -1497,7 +1497,9 @@ int epn_inter_ungroup_det_bf16(const epn_inter_desc *d, const void *grad_grouped
  * broadcast index) on channels-last data, where it is a gather of whole [a][c] rows, and its autograd backward.
  *   src [b][p1][row_bytes], idx i32[b][p2] -> dst [b][p2][row_bytes]            (row_bytes % 16 == 0, any element type)
  *   epn_scatter_rows: grad_src [b][p1][row_bytes] = 0, then row idx[b][p] <- grad_dst[b][p] (indices distinct per cloud,
- *   as FPS indices are: plain stores, deterministic) */
+ *   as FPS indices are: plain stores, deterministic)
+ * An index outside [0, p1) is skipped by all three entries: epn_gather_rows does NOT write that destination row (it keeps
+ * whatever it held), epn_scatter_rows / epn_scatter_rows_add neither store nor add that gradient row. */
 int epn_gather_rows(const void *src, const int32_t *idx, void *dst, int b, int p1, int p2, long long row_bytes,
                     epn_stream_t stream);
 int epn_scatter_rows(const void *grad_dst, const int32_t *idx, void *grad_src, int b, int p1, int p2, long long row_bytes,
