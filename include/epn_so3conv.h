@@ -466,6 +466,88 @@ int epn_point_normals_f32(const void *workspace, int64_t n, const float *qry, in
 int epn_orient_patches_f32(const float *patches, const float *normals, int64_t k, int n_sample, float *axis, float *out,
                            epn_stream_t stream);
 
+/* TSDF fusion: a window of depth frames -> the surface points of ONE fragment (csrc/tsdf_fusion.hip,
+ * csrc/tsdf_math.h).  The reference makes its fragments on the host with open3d (SPConvNets/datasets/preprocess/run_fusion.py:20-49
+ * with the settings of preprocess/tool.py:17-27): per window of frames_per_frag = 50 frames a ScalableTSDFVolume (voxel_length
+ * 3.0 / 512, sdf_trunc 0.04, depth scale 1000, depth truncation 6 m) integrates every frame, then extract_point_cloud() and
+ * estimate_normals() (which is epn_point_normals_f32).  This is open3d's algorithm made deterministic, positions only: no colour
+ * (nothing downstream reads it) and not the extract's gradient normals (the reference overwrites them).  Differences from open3d a
+ * maintainer should know: the arithmetic is fp64 from the fp32 depth on, where open3d's is float (and sdf / sdf_trunc is a
+ * division where open3d multiplies by a reciprocal); the unit directory is a dense array over a caller-given box, not a hash map,
+ * so a sample outside the box is flagged instead of allocated; blocks and points come in the fixed order below, where open3d's is
+ * its hash map's; a sample touches the units of the CORNERS of its +- sdf_trunc box (the same set as open3d's box walk under the
+ * sdf_trunc rule below).  Argued from open3d's algorithm, not run against it.
+ * All arithmetic below is fp64 with every operation rounded on its own (no fma), written in the order to evaluate it, unless
+ * it says fp32; a numpy restatement reproduces every output bit for bit (tests/tsdf_ref.py).
+ *
+ * epn_tsdf_fuse_f32: depth u16[F,H,W], cam2base f64[F,4,4] and base2cam f64[F,4,4] (row-major; each frame's pose in the first
+ *   frame's coordinates and its inverse -- the caller inverts, the device never does; only the first three rows are read), the
+ *   pinhole fx, fy, cx, cy, depth_scale, depth_trunc, voxel_length, sdf_trunc, stride (open3d's depth_sampling_stride: 4), the unit
+ *   box lo_x.., dim_x.., max_blocks -> block_unit i32[max_blocks,3], block_mask u64[max_blocks], tsdf f32[max_blocks,16,16,16],
+ *   weight i32[max_blocks,16,16,16] (outputs, not scratch: they are what makes the entry testable; both 16-byte aligned), status
+ *   i32[4] = {n_blocks, flags, n_outside, 0}, all on the device.
+ *   depth           d = (float)raw / (float)depth_scale, one fp32 division; d = 0 where raw == 0 or (double)d > depth_trunc.  0 means
+ *                   "no measurement".  Everything after is fp64 from this fp32 value.
+ *   units           a unit is 16^3 voxels (open3d's volume_unit_resolution), unit_length = 16 * voxel_length; the unit index of a
+ *                   coordinate is floor(x / unit_length): floor, not truncation.  The directory is a dense array of 64-bit frame
+ *                   masks over the box of units lo <= unit < lo + dim per axis, entry ((ux - lo_x) dim_y + (uy - lo_y)) dim_z +
+ *                   (uz - lo_z); a non-zero mask means "allocated".  There is no hash table: ranks come from a prefix sum
+ *                   over the directory in this linear order, so nothing depends on arrival order.
+ *   touch           (ScalableTSDFVolume::Integrate, first half) every pixel (u, v) with u % stride == 0, v % stride == 0 and d != 0:
+ *                   c = (((u - cx) * d) / fx, ((v - cy) * d) / fy, d); p_i = ((T_i0 c_0 + T_i1 c_1) + T_i2 c_2) + T_i3 with T =
+ *                   cam2base[f]; per axis lo_i = floor((p_i - sdf_trunc) / unit_length), hi_i = floor((p_i + sdf_trunc) /
+ *                   unit_length); bit f is set (64-bit atomicOr: order-independent) in every unit of {lo_0, hi_0} x {lo_1, hi_1} x
+ *                   {lo_2, hi_2}.  sdf_trunc <= 8 * voxel_length is required, so that these corners are the whole index box (at
+ *                   most 2 units per axis).  A unit outside the caller's box (or a non-finite index) is not allocated: flags bit
+ *                   0 is raised and n_outside counts the samples (pixel, frame) with at least one such unit.  Nothing is
+ *                   dropped silently.
+ *   blocks          the allocated units take ranks 0..n_blocks-1 in ascending directory order; block_unit[r] = the unit's index,
+ *                   block_mask[r] = its mask.  n_blocks > max_blocks raises flags bit 1; ranks >= max_blocks are neither
+ *                   integrated nor written (rows past min(n_blocks, max_blocks) are left untouched), and the extract treats them
+ *                   as absent.
+ *   integrate       (UniformTSDFVolume::IntegrateWithDepthToCameraDistanceMultiplier) per voxel (x, y, z) of a block, (tsdf, w) =
+ *                   (0, 0), then for exactly the frames of the block's mask in ascending f (open3d integrates only the units the
+ *                   current frame touched):
+ *                   1. centre_i = ((16 unit_i + idx_i) + 0.5) * voxel_length;
+ *                   2. c = the centre under base2cam[f], summed as in touch;
+ *                   3. skip unless c_2 > 0;
+ *                   4. u_f = ((c_0 * fx) / c_2 + cx) + 0.5, v_f = ((c_1 * fy) / c_2 + cy) + 0.5; skip unless 0 <= u_f < W and
+ *                      0 <= v_f < H; pixel (pu, pv) = ((int)u_f, (int)v_f);
+ *                   5. skip when that pixel's d == 0;
+ *                   6. a = (pu - cx) / fx, b = (pv - cy) / fy, sdf = (d - c_2) * sqrt((a a + b b) + 1); skip unless sdf >
+ *                      -sdf_trunc (strict);
+ *                   7. t = (float)min(1, sdf / sdf_trunc); then in fp32, each operation rounded on its own, tsdf = (tsdf * (float)w
+ *                      + t) / (float)(w + 1); w += 1.
+ *                   A voxel no frame observed keeps (0, 0).  tsdf and weight are indexed [block][x][y][z], z fastest.
+ * epn_tsdf_extract_f32: tsdf, weight, block_unit, the box and max_blocks of a fuse and its workspace (which holds n_blocks and the
+ *   directory's ranks) -> points f32[max_points,3], status i32[2] = {M, flags}.  (ScalableTSDFVolume::ExtractPointCloud, positions.)
+ *   A voxel takes part when w != 0 and -0.98f <= tsdf < 0.98f (fp32 comparisons).  For a voxel that takes part, with value f0 and
+ *   centre p, and each axis a = 0, 1, 2: its +1 neighbour on that axis -- looked up through the directory when it lies in the
+ *   next unit; an absent unit, a unit outside the box or a rank >= min(n_blocks, max_blocks) gives no neighbour -- must take part
+ *   too, with value f1; a point is emitted where (double)f0 * (double)f1 < 0, with coordinate (p_a r1 + (p_a + voxel_length) r0) /
+ *   (r0 + r1) on axis a, r0 = |f0|, r1 = |f1|, and p on the other two; stored as fp32.  Order: ascending block rank, then voxel
+ *   x, y, z with z fastest, then axis 0, 1, 2 (per-block counts, one scan, the write pass).  M > max_points raises flags bit 0
+ *   and nothing is written beyond max_points rows.
+ * Workspace: epn_tsdf_fuse_workspace_bytes(F, H, W, stride, dim_x, dim_y, dim_z, max_blocks) bytes (host-only; 0 for arguments the
+ *   fuse refuses: 64 + 12 bytes per directory entry + 4 per block, tile and touch workgroup), 8-byte aligned, initialised by the
+ *   fuse itself and read by the extract.  Launches: fuse six (init, touch, count, scan, rank, integrate -- one workgroup per
+ *   block, frames looped inside), extract three.  The only atomic is the touch's 64-bit OR; no floating-point atomics; no loop
+ *   bound depends on data; every directory, pool and pixel index is range-checked where it is read; two runs are bitwise equal.
+ * Refusals, decided before any HIP runtime call: EPN_EINVAL for F outside 1..64, H or W outside 1..16384, stride < 1, a
+ *   non-finite or non-positive fx, fy, depth_scale (also as a float), depth_trunc, voxel_length or sdf_trunc, a non-finite cx or
+ *   cy, sdf_trunc > 8 * voxel_length, a dimension < 1, a box product over 2^24, |lo| > 2^24, max_blocks outside 1..2^17 (2^17
+ *   blocks hold fewer than 2^31 points), max_points < 0, tsdf or weight not 16-byte aligned; then EPN_ENULL for a NULL pointer
+ *   (points only when max_points > 0); then EPN_EWORKSPACE for a workspace that is NULL, not 8-byte aligned or too small. */
+size_t epn_tsdf_fuse_workspace_bytes(int F, int H, int W, int stride, int dim_x, int dim_y, int dim_z, int max_blocks);
+int epn_tsdf_fuse_f32(const uint16_t *depth, int F, int H, int W, const double *cam2base, const double *base2cam, double fx,
+                      double fy, double cx, double cy, double depth_scale, double depth_trunc, double voxel_length,
+                      double sdf_trunc, int stride, int lo_x, int lo_y, int lo_z, int dim_x, int dim_y, int dim_z, int max_blocks,
+                      int32_t *block_unit, uint64_t *block_mask, float *tsdf, int32_t *weight, int32_t *status, void *workspace,
+                      size_t workspace_bytes, epn_stream_t stream);
+int epn_tsdf_extract_f32(const float *tsdf, const int32_t *weight, const int32_t *block_unit, int max_blocks, int lo_x, int lo_y,
+                         int lo_z, int dim_x, int dim_y, int dim_z, double voxel_length, float *points, int max_points,
+                         int32_t *status, void *workspace, size_t workspace_bytes, epn_stream_t stream);
+
 /* Rotation estimation: what turns RegSO3ConvModel's head output into a rotation, the labels a training step needs and the
  * angular error the reference reports.  All tensors are contiguous device memory, float or int32; anchors
  * f32[A,3,3], 1 <= A <= 64.  Arithmetic is fp64 on the fp32 inputs and every output is rounded once to fp32.  One wave per
