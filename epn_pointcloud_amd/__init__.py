@@ -31,7 +31,7 @@ def install_vgtk_alias():
 
 
 _MATCHING = ("match_descriptors", "evaluate_fragment_pair", "evaluate_scene", "register_scene", "register_fragment_pair",
-             "registration_errors", "registration_recall", "RegistrationResult")
+             "registration_errors", "registration_recall", "RegistrationResult", "refine_registration", "refine_scene", "IcpResult")
 _ALIGNMENT = ("decode_rotation", "evaluate_alignment")
 _DATA = ("pack_clouds", "modelnet_batch", "modelnet_alignment_batch", "ModelNetBatch", "pack_correspondences",
          "fragment_pair_batch", "FragmentPairBatch")
@@ -41,7 +41,8 @@ _OPTIM = ("FlatAdam",)
 
 def __getattr__(name):
     """`epn_pointcloud_amd.match_descriptors` / `.evaluate_fragment_pair` / `.evaluate_scene` / `.register_scene` /
-    `.register_fragment_pair` / `.registration_errors` / `.registration_recall` (matching.py) and
+    `.register_fragment_pair` / `.registration_errors` / `.registration_recall` / `.refine_registration` / `.refine_scene`
+    (matching.py) and
     `.decode_rotation` / `.evaluate_alignment` (alignment.py) and `.pack_clouds` / `.modelnet_batch` /
     `.modelnet_alignment_batch` / `.pack_correspondences` / `.fragment_pair_batch` (data.py) and `.evaluate_classification` (classification.py) and `.FlatAdam` (optim.py), resolved on first use so that importing the package -- the
     build recipe does -- still needs no torch."""

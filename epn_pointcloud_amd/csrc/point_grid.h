@@ -108,4 +108,54 @@ __device__ __forceinline__ unsigned long long member_key(float d2, int row) {
     return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)row;
 }
 
+// The answer of epn_point_grid_nn_f32 for the wave's query (qx, qy, qz), the same in every lane: key = the smallest member key
+// among the grid's points with d2 <= r2 (NONE without one, and for a non-finite query or n == 0, which read nothing of the
+// grid), and the winner's coordinates as its record holds them.  exclude_row skips the candidate whose row is q.  Every lane of
+// the wave calls it.  A kernel that does not use the coordinates pays nothing for them.
+struct Nearest {
+    unsigned long long key;
+    float x, y, z;
+};
+
+__device__ __forceinline__ Nearest nearest_member(const Head *__restrict__ head, const Slot *__restrict__ slots,
+                                                  const int4 *__restrict__ records, int n, int log2cap, double edge, float qx,
+                                                  float qy, float qz, float r2, int exclude_row, int q, int lane) {
+    Nearest best;
+    best.key = NONE;
+    best.x = best.y = best.z = 0.0f;
+    if (n > 0 && isfinite(qx) && isfinite(qy) && isfinite(qz)) {
+        const Cells cells = find_cells(head, slots, n, log2cap, edge, qx, qy, qz, lane);
+        for (int base = 0; base < cells.total; base += 64) {   // every lane runs every pass: the shuffles read all of them
+            const int at = record_of(cells, base + lane, n);
+            if (at >= 0) {
+                const int4 p = records[at];
+                const int row = p.w;
+                const float px = __int_as_float(p.x), py = __int_as_float(p.y), pz = __int_as_float(p.z);
+                const float d2 = dist2(px, py, pz, qx, qy, qz);
+                if (d2 <= r2 && !(exclude_row && row == q)) {
+                    const unsigned long long k = member_key(d2, row);
+                    if (k < best.key) {
+                        best.key = k;
+                        best.x = px; best.y = py; best.z = pz;
+                    }
+                }
+            }
+        }
+        unsigned long long low = best.key;
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            const unsigned long long o = __shfl_xor(low, s, 64);
+            low = o < low ? o : low;
+        }
+        // a row occurs once in the grid, so one lane holds the winning key: the lowest such lane hands its coordinates out
+        const unsigned long long holders = __ballot(best.key == low && low != NONE);
+        const int owner = holders ? __ffsll((long long)holders) - 1 : 0;
+        best.key = low;
+        best.x = __shfl(best.x, owner, 64);
+        best.y = __shfl(best.y, owner, 64);
+        best.z = __shfl(best.z, owner, 64);
+    }
+    return best;
+}
+
 }  // namespace epn_grid

@@ -168,26 +168,7 @@ __global__ __launch_bounds__(QW * 64) void grid_nn_kernel(const Head *__restrict
     unsigned long long best = NONE;
     if (q < m && n > 0) {
         const float qx = qry[3 * (size_t)q], qy = qry[3 * (size_t)q + 1], qz = qry[3 * (size_t)q + 2];
-        if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
-            const Cells cells = find_cells(head, slots, n, log2cap, edge, qx, qy, qz, lane);
-            for (int base = 0; base < cells.total; base += 64) {   // every lane runs every pass: the shuffles read all of them
-                const int at = record_of(cells, base + lane, n);
-                if (at >= 0) {
-                    const int4 p = records[at];
-                    const int row = p.w;
-                    const float d2 = dist2(__int_as_float(p.x), __int_as_float(p.y), __int_as_float(p.z), qx, qy, qz);
-                    if (d2 <= r2 && !(exclude_row && row == q)) {
-                        const unsigned long long k = member_key(d2, row);
-                        best = k < best ? k : best;
-                    }
-                }
-            }
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) {
-                const unsigned long long o = __shfl_xor(best, s, 64);
-                best = o < best ? o : best;
-            }
-        }
+        best = nearest_member(head, slots, records, n, log2cap, edge, qx, qy, qz, r2, exclude_row, q, lane).key;
     }
     if (q < m && lane == 0) {
         nn_idx[q] = best == NONE ? -1 : (int32_t)(unsigned)(best & 0xFFFFFFFFull);

@@ -13,6 +13,8 @@ arrays, like the reference's.  A whole scene is one nearest-neighbour launch and
 Without ground truth: `register_scene` / `register_fragment_pair` turn the mutual matches into the rigid transform between
 the fragments (RANSAC over three-point samples and a refit; epn_ransac_register_f64, DESIGN.md 3.1c, csrc/ransac_register.hip),
 and `registration_errors` / `registration_recall` score such transforms against known ones on the host.
+`refine_registration` / `refine_scene` then refine such a transform on the dense clouds by ICP, point-to-point or point-to-plane
+(epn_icp_refine_f32, DESIGN.md 3.1m, csrc/icp_refine.hip): open3d's registration_icp, the whole loop on the device.
 """
 import collections
 
@@ -138,3 +140,81 @@ def registration_recall(T_est, T_gt, rre_deg=15.0, rte=0.3):
     learned-registration literature; both are parameters) -> float in [0, 1], 0.0 without pairs."""
     r, t = registration_errors(T_est, T_gt)
     return float(np.mean((r < rre_deg) & (t < rte))) if r.size else 0.0
+
+
+IcpResult = collections.namedtuple("IcpResult", "T fitness inlier_rmse iterations status trace")
+IcpResult.__doc__ = """refine_registration's result, host values: T float64 [4,4] taking src into the target's frame; fitness
+(correspondences / source points) and inlier_rmse of the last live iteration -- after a stop those of T itself, otherwise those of
+the transform the last iteration started from; iterations, the number of iterations that updated T; status, the flags met (bit
+0: the stop test was met, bit 1: too few correspondences, bit 2: a singular system -- with 1 or 2 T is the last good transform);
+trace float64 [max_iter,20], per iteration {T after it (16), count, sum of squared distances, rmse, flags}."""
+
+
+def _invert_rigid(T):
+    """The inverse of a rigid [4,4] in numpy fp64: (R^T, -R^T t).  The ONE place where refine_scene turns a pair's transform."""
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    out = np.eye(4)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -(T[:3, :3].T @ T[:3, 3])
+    return out
+
+
+def refine_registration(src_points, tgt_points_or_grid, T_init, max_dist, *, tgt_normals=None, max_iter=30, rel_fitness=1e-6,
+                        rel_rmse=1e-6):
+    """(src_points f32 [m,3]; tgt_points_or_grid: f32 [n,3] or its PointGrid, built with max_radius >= max_dist; T_init [4,4]
+    taking src into the target's frame; max_dist: the correspondence distance) -> IcpResult: open3d's registration_icp on the
+    device, as include/epn_so3conv.h states it (epn_icp_refine_f32).  The TARGET is the gridded cloud; every
+    iteration moves the source by the current transform and pairs each of its points with the nearest target point within
+    max_dist.  Without tgt_normals the update is point-to-point (Horn's fit), with tgt_normals f32 [n,3] (PointGrid.normals)
+    point-to-plane.  The defaults are open3d's ICPConvergenceCriteria.  The whole loop runs on the device; the result is read
+    back once, at the end.  A matched coordinate beyond 64 raises ValueError naming the flag's bit, as PointGrid does; too few
+    correspondences and a singular system are returned in status, with the last good transform."""
+    from .correspondence import _grid
+    grid = _grid(tgt_points_or_grid, "tgt_points", float(max_dist))
+    T0 = torch.as_tensor(np.ascontiguousarray(np.asarray(torch.as_tensor(T_init).cpu(), dtype=np.float64).reshape(4, 4)))
+    T, trace, iterations, status, _, _ = grouping.icp_refine(grid._workspace, grid.n, src_points, T0.to(grid.points.device), max_dist,
+                                                             tgt_normals=tgt_normals, max_iter=max_iter, rel_fitness=rel_fitness,
+                                                             rel_rmse=rel_rmse)
+    packed = torch.cat((T.reshape(-1), trace.reshape(-1), iterations.to(torch.float64), status.to(torch.float64))).cpu().numpy()
+    T, trace, iterations, status = packed[:16].reshape(4, 4), packed[16:-2].reshape(-1, 20), int(packed[-2]), int(packed[-1])
+    if status & 8:
+        raise ValueError("refine_registration: status " + grouping.ICP_FLAGS[3] + f" (flags = {status})")
+    m = src_points.shape[0]
+    live = min(iterations + (1 if status else 0), trace.shape[0]) - 1   # a stop writes one more live record than it updates T
+    count, rmse = (trace[live, 16], trace[live, 18]) if live >= 0 else (0.0, 0.0)
+    return IcpResult(T, float(count) / m if m else 0.0, float(rmse), iterations, status, trace)
+
+
+def refine_scene(clouds, pairs, T_init, max_dist, *, normals=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
+    """(clouds: F tensors f32 [n_f,3], each in its fragment's own frame; pairs int [P,2] of (src fragment, tgt fragment); T_init
+    f64 [P,4,4] as RegistrationResult.T holds it: taking tgt coordinates into src coordinates) -> (T float64 [P,4,4] in the same
+    convention, results: the P IcpResults).  The pair's TGT fragment is the gridded cloud and its SRC fragment the moving one, so
+    the stage runs from the inverse of T_init[p] (src into tgt) and its result is inverted back: both in _invert_rigid, numpy fp64
+    on the host.  One PointGrid is built per fragment that appears as a tgt, with max_radius = max_dist (or the normals' radius,
+    if that is larger).  normals: None (point-to-point), a float radius (the normals of every tgt fragment are estimated once,
+    PointGrid.normals(radius=normals, max_nn=30)), or a list of F tensors f32 [n_f,3] (entries of fragments that are never a tgt
+    may be None).  Every pair is one refine_registration call, and equals it bit for bit."""
+    from .correspondence import PointGrid
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    T_init = np.asarray(torch.as_tensor(T_init).cpu(), dtype=np.float64).reshape(-1, 4, 4)
+    if T_init.shape[0] != pairs.shape[0]:
+        raise ValueError(f"T_init must be [{pairs.shape[0]},4,4], got {T_init.shape}")
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= len(clouds)):
+        raise ValueError(f"pairs must index fragments 0..{len(clouds) - 1}")
+    estimate = isinstance(normals, (int, float)) and not isinstance(normals, bool)
+    if normals is not None and not estimate and len(normals) != len(clouds):
+        raise ValueError(f"normals must be a radius or hold one entry per fragment, got {len(normals)} for {len(clouds)}")
+    grids, nrm = {}, {}
+    for j in sorted(set(pairs[:, 1].tolist())):
+        grids[j] = PointGrid(clouds[j], max(float(max_dist), float(normals)) if estimate else float(max_dist))
+        nrm[j] = None if normals is None else (grids[j].normals(radius=float(normals), max_nn=30).normals if estimate
+                                               else normals[j])
+        if normals is not None and nrm[j] is None:
+            raise ValueError(f"normals[{j}] is None, but fragment {j} is the tgt of a pair")
+    T, results = np.tile(np.eye(4), (pairs.shape[0], 1, 1)), []
+    for p, (i, j) in enumerate(pairs.tolist()):
+        r = refine_registration(clouds[i], grids[j], _invert_rigid(T_init[p]), max_dist, tgt_normals=nrm[j], max_iter=max_iter,
+                                rel_fitness=rel_fitness, rel_rmse=rel_rmse)
+        results.append(r)
+        T[p] = _invert_rigid(r.T)
+    return T, results

@@ -243,6 +243,57 @@ def orient_patches(patches, normals, out=None):
     return out, axis
 
 
+MAX_ICP_POINTS = 2 ** 20
+MAX_ICP_ITER = 1024
+ICP_FLAGS = ("bit 0: converged (the stop test was met)",
+             "bit 1: too few correspondences (fewer than 3, or 6 for point-to-plane)",
+             "bit 2: the iteration's system is singular or ill-conditioned",
+             "bit 3: a matched coordinate exceeds 64 in magnitude (or a normal component exceeds 1)")
+
+
+def icp_refine(workspace, n, src, T_init, max_dist, tgt_normals=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
+               return_sums=False, return_nn=False):
+    """(workspace from point_grid_build of the n target points, src f[m,3], T_init f64 [4,4] on the device taking src into the
+    target's frame, float max_dist <= the build's max_radius, tgt_normals f[n,3] or None) -> (T f64 [4,4], trace f64
+    [max_iter,20], iterations int32 [1], status int32 [1], sums int64 [32] or None, nn_idx int32 [m] or None), device tensors:
+    ICP from T_init, point-to-point without normals and point-to-plane with them; a trace record is {T after the iteration
+    (16), count, sum of squared distances, rmse, flags} (epn_icp_refine_f32, include/epn_so3conv.h; no counterpart in the
+    reference -- the host tool for this step is open3d's registration_icp).  Nothing is read back."""
+    from ...data import _tensor
+    lib = _lib.get_lib()
+    src = _tensor(src, "src", (None, 3), torch.float32)
+    T_init = _tensor(T_init, "T_init", (4, 4), torch.float64)
+    workspace = _tensor(workspace, "workspace", (None,), torch.int64)
+    n, m, r, K = int(n), src.shape[0], float(max_dist), int(max_iter)
+    if tgt_normals is not None:
+        tgt_normals = _tensor(tgt_normals, "tgt_normals", (n, 3), torch.float32)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"max_dist must be finite and > 0, got {max_dist}")
+    if not 0 <= K <= MAX_ICP_ITER:
+        raise ValueError(f"max_iter must be in 0..{MAX_ICP_ITER}, got {max_iter}")
+    if m > MAX_ICP_POINTS:
+        raise ValueError(f"a call takes at most 2^20 source points, got {m}")
+    for name, v in (("rel_fitness", rel_fitness), ("rel_rmse", rel_rmse)):
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"{name} must be finite and >= 0, got {v}")
+    _lib.same_device(workspace, src, T_init, tgt_normals)
+    f64, i32 = dict(dtype=torch.float64, device=src.device), dict(dtype=torch.int32, device=src.device)
+    T, trace = torch.empty((4, 4), **f64), torch.empty((K, 20), **f64)
+    iterations, status = torch.empty((1,), **i32), torch.empty((1,), **i32)
+    sums = torch.empty((32,), dtype=torch.int64, device=src.device) if return_sums else None
+    nn_idx = torch.empty((m,), **i32) if return_nn else None
+    ws_bytes = int(lib.epn_icp_workspace_bytes(m))
+    ws = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=src.device)
+    _lib.check(lib.epn_icp_refine_f32(ctypes.c_void_p(workspace.data_ptr()), n, _lib.dev_ptr(tgt_normals, "tgt_normals"),
+                                      _lib.dev_ptr(src, "src"), m, _lib.dev_ptr(T_init, "T_init", torch.float64), r, K,
+                                      float(rel_fitness), float(rel_rmse), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8,
+                                      _lib.dev_ptr(T, "T", torch.float64), _lib.dev_ptr(trace, "trace", torch.float64),
+                                      _lib.dev_ptr(iterations, "iterations", torch.int32),
+                                      _lib.dev_ptr(status, "status", torch.int32), _lib.dev_ptr(sums, "sums", torch.int64),
+                                      _lib.dev_ptr(nn_idx, "nn_idx", torch.int32), _lib.stream_of(src)), "icp_refine")
+    return T, trace, iterations, status, sums, nn_idx
+
+
 def _scene_tables(frag_off, pairs, device):
     """Host copies (contiguous numpy: what the library's argument checks read) and device copies (what its kernels read) of a
     scene's tables, with out_off / tgt_off computed from them (include/epn_so3conv.h, "Scene tables")."""

@@ -466,6 +466,93 @@ int epn_point_normals_f32(const void *workspace, int64_t n, const float *qry, in
 int epn_orient_patches_f32(const float *patches, const float *normals, int64_t k, int n_sample, float *axis, float *out,
                            epn_stream_t stream);
 
+/* ICP refinement: the dense alignment after epn_ransac_register_f64 (csrc/icp_refine.hip, csrc/icp_math.h).  This
+ * is open3d's registration_icp with TransformationEstimationPointToPoint or TransformationEstimationPointToPlane and
+ * ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration), made deterministic.  It is argued from open3d's
+ * algorithm; open3d is not installed where this was written, and the stage has not been run against it.  The contract fixes the
+ * result, not the schedule.
+ *
+ * epn_icp_refine_f32: the target's grid (grid_workspace and n, as epn_point_grid_nn_f32 takes them), tgt_normals f32[n,3] or NULL
+ *   (NULL: point-to-point; otherwise point-to-plane), src f32[m,3], T_init f64[4,4] row-major taking src into the target's frame
+ *   (only its first three rows are read), max_dist, max_iter, rel_fitness, rel_rmse -> all on the device: T f64[4,4] (bottom row
+ *   written 0 0 0 1; T may be T_init), trace f64[max_iter,20], iterations i32[1], status i32[1], and, each NULL-able, sums i64[32]
+ *   and nn_idx i32[m].
+ *   Iteration k = 0 .. max_iter-1 starts from T_k (T_0 = T_init) and does, in this order:
+ *   transform     q_i = (float)fma(T_i0, s_0, fma(T_i1, s_1, fma(T_i2, s_2, T_i3))) for every source point s, the fp32
+ *                 coordinates widened to fp64: three explicit fp64 fmas per component (the chain of csrc/rigid_fit.h's
+ *                 sq_residual), rounded once to fp32.
+ *   correspond    the answer of epn_point_grid_nn_f32 for the query q with radius = max_dist and exclude_row = 0: individually
+ *                 rounded fp32 d2, r2 = (float)(max_dist * max_dist), inclusive, the lowest row on a tie, only the points that
+ *                 took part in the build (its ref_valid mask), nothing for a non-finite or far q.  p = that point, as fp32.
+ *   range         a matched pair is OUT OF RANGE when not |p_i| <= 64 and |q_i| <= 64 on every axis (NaN counts), and in
+ *                 point-to-plane mode when not |n_i| <= 1 for every component of the normal n = tgt_normals[row of p].  Such a
+ *                 pair adds to no sum below; it is counted in sum 30, and any such pair raises flag bit 3 (below).
+ *   accumulate    every other matched pair adds one term to each int64 sum of a row of 32.  All values are fp64, every
+ *                 operation rounded on its own (no fma); d = q - p per axis, dd = (d0 d0 + d1 d1) + d2 d2.  A term is
+ *                 rint((a b) * scale), the product rounded once before the exact power-of-two scaling, ties to even (the rule
+ *                 of epn_point_normals_f32's moments).  Origin: the coordinate origin of the target's frame.  Quanta: 2^-32 for
+ *                 the linear sums, 2^-24 for the product sums.
+ *                   point-to-point   [0] count; [1..3] p_i 2^32; [4..6] q_i 2^32; [7 + 3i + j] (p_i q_j) 2^24; [16] dd 2^24.
+ *                   point-to-plane   c = q x n (c0 = q1 n2 - q2 n1, c1 = q2 n0 - q0 n2, c2 = q0 n1 - q1 n0), r = (d0 n0 + d1 n1) +
+ *                                    d2 n2, J = (c0, c1, c2, n0, n1, n2).  [0] count; [1..21] (J_i J_j) 2^24 for i <= j, row-major
+ *                                    (00, 01, .., 05, 11, ..); [22 + i] (J_i r) 2^24; [28] (r r) 2^24; [29] dd 2^24.
+ *                 [30] = the number of out-of-range pairs; the other entries are 0.
+ *                 Why no sum leaves int64: in range, |p_i|, |q_i| <= 2^6 and |n_i| <= 1 give |c_i| <= 2^7, |d_i| <= 2^7, |r| <= 3 *
+ *                 2^7, so every product is at most r r <= 9 * 2^14 < 2^18 (p_i q_j <= 2^12, dd <= 3 * 2^14, J_i r <= 3 * 2^14) up to
+ *                 rounding, a product term at most 2^42 + 1 and a linear term at most 2^38; with m <= 2^20 points every sum is
+ *                 below 2^62 + 2^20 < 2^63.  Hence m <= 2^20 (EPN_EINVAL beyond, decided on the host) and the range +-64.
+ *                 (2^18 pads the largest product, 9 * 2^14: by the unpadded figure 2^21 points would still fit, 9 * 2^59 < 2^63,
+ *                 and 2^22 would not.  The limit refused beyond is the padded bound's 2^20: one bit of slack, stated, not used.)
+ *   step          N = count, ssd = [dd sum] / 2^24, rmse = sqrt(ssd / N) (0 when N = 0: open3d's inlier_rmse is the Euclidean one
+ *                 in both variants), fitness = N / m.  The first that applies, flag bits in brackets:
+ *                   [3] an out-of-range pair;
+ *                   [1] N < 3 (point-to-point) or N < 6 (point-to-plane);
+ *                   [0] k > 0 and |fitness_k - fitness_{k-1}| < rel_fitness and |rmse_k - rmse_{k-1}| < rel_rmse: open3d's test,
+ *                       which compares two successive evaluations; this is "converged", not a failure;
+ *                   [2] the solve below is singular;
+ *                   otherwise T_{k+1} = dT T_k, no flag.
+ *                 With any flag T_{k+1} = T_k and the loop STOPS: every later iteration is a no-op whose trace record repeats this
+ *                 one.  iterations = the number of iterations that updated T (open3d's loop count when it breaks); status = the OR
+ *                 of the flags met (0: max_iter updates were made without the stop test being met).
+ *   solve, point-to-point   sp = S_p / 2^32, sq = S_q / 2^32, pbar = sp / N, qbar = sq / N, C_ij = S_pq,ij / 2^24 - (sp_i sq_j) / N;
+ *                 (dR, margin) = the projection of epn_so3_mean_f32 applied to C, dt = pbar - dR qbar (csrc/rigid_fit.h's
+ *                 fit_finish, the fit of epn_ransac_register_f64).  Singular: not margin > 1e-6.
+ *   solve, point-to-plane   A = the symmetric 6 x 6 of sums [1..21] / 2^24, b = sums [22..27] / 2^24.  A = L D L^T without pivoting,
+ *                 k ascending: d_k = A_kk - sum_{j<k} (L_kj d_j) L_kj, L_ik = (A_ik - sum_{j<k} (L_ij d_j) L_kj) / d_k, sums from the
+ *                 left in ascending j.  Singular: not d_k > 2^-20 A_kk for some k (all normals parallel, a single plane, ...), or
+ *                 a non-finite solution.  L y = -b (ascending), z = y / d, L^T x = z (descending); w = x[0..3), dt = x[3..6).
+ *                 dR = the Cayley map (I - [w]x / 2)^-1 (I + [w]x / 2) in closed form: a = w / 2, aa = (a0 a0 + a1 a1) + a2 a2,
+ *                 k = 1 - aa, den = 1 + aa, dR_ii = (k + w_i a_i) / den, dR_01 = (w0 a1 - w2) / den, dR_02 = (w0 a2 + w1) / den,
+ *                 dR_10 = (w1 a0 + w2) / den, dR_12 = (w1 a2 - w0) / den, dR_20 = (w2 a0 - w1) / den, dR_21 = (w2 a1 + w0) / den.
+ *                 This is the ONE deliberate difference from open3d, which composes the Euler rotations Rz(w2) Ry(w1) Rx(w0):
+ *                 the Cayley map needs + - x / only, is an exact rotation for every w, agrees with open3d's to second order in w
+ *                 and has the same fixed point (w = 0), so a restatement follows it without a libm in the way.
+ *   compose       rows 0..2: T'_ij = (dR_i0 T_0j + dR_i1 T_1j) + dR_i2 T_2j, and then T'_i3 += dt_i.
+ *   All of "step" is fp64 with every operation rounded on its own, except inside the projection, which is compiled as it is
+ *   for epn_ransac_register_f64; so T is reproducible bit for bit between runs, and a restatement (tests/icp_ref.py) meets it
+ *   within a bound, while correspondences, counts and sums are integers and are met exactly.
+ *   trace         record k = {T_{k+1} (16), N, ssd, rmse, flags} of iteration k, as doubles.  The count and rmse of a record are
+ *                 those of T_k, the transform the iteration STARTED from: max_iter iterations make max_iter searches, where
+ *                 open3d makes one more to evaluate its final transform.  After a stop the last live record's N and rmse ARE those
+ *                 of the final T.  sums and nn_idx are those of the last live iteration (nn_idx: the row of p, or -1).
+ *   Degenerate sizes: m == 0 or max_iter == 0 succeeds with T = T_init, iterations = 0, status = 0, every trace record {T_init, 0,
+ *   0, 0, 0}, sums 0 and nn_idx -1 (one launch).  n == 0 (an empty grid) matches nothing: flag bit 1 at iteration 0.
+ *   Launches: icp_accumulate then icp_solve per iteration, 2 * max_iter in all, on the given stream; no host synchronisation, no
+ *   memset, no atomics: the call can be captured into a HIP graph as one linear chain.  icp_accumulate: one wave per source
+ *   point, four per workgroup, at most 1024 workgroups striding over the points (the result does not depend on that number);
+ *   every workgroup writes one row of 32 sums to the workspace; icp_solve adds the rows.  Integer sums: two runs are bitwise equal.
+ *   Workspace: epn_icp_workspace_bytes(m) bytes (host-only; 0 outside 0 <= m <= 2^20), 16-byte aligned; written by the call and
+ *   not read before it is written.  It must not be shared by two calls in flight.
+ *   Refusals, decided before any HIP runtime call: EPN_EINVAL for n outside 0..2^22, m outside 0..2^20, max_dist not finite or
+ *   <= 0, max_iter outside 0..1024, rel_fitness or rel_rmse negative or not finite, a grid_workspace address and n that no build
+ *   was called with, or max_dist > max_radius of that build; then EPN_ENULL for T_init, T, iterations, status, src (m > 0) or
+ *   trace (max_iter > 0) NULL; then EPN_EWORKSPACE for a workspace that is NULL, misaligned or too small. */
+size_t epn_icp_workspace_bytes(int64_t m);
+int epn_icp_refine_f32(const void *grid_workspace, int64_t n, const float *tgt_normals, const float *src, int64_t m,
+                       const double *T_init, double max_dist, int max_iter, double rel_fitness, double rel_rmse, void *workspace,
+                       size_t workspace_bytes, double *T, double *trace, int32_t *iterations, int32_t *status, int64_t *sums,
+                       int32_t *nn_idx, epn_stream_t stream);
+
 /* TSDF fusion: a window of depth frames -> the surface points of ONE fragment (csrc/tsdf_fusion.hip,
  * csrc/tsdf_math.h).  The reference makes its fragments on the host with open3d (SPConvNets/datasets/preprocess/run_fusion.py:20-49
  * with the settings of preprocess/tool.py:17-27): per window of frames_per_frag = 50 frames a ScalableTSDFVolume (voxel_length
