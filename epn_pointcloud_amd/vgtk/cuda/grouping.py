@@ -243,6 +243,41 @@ def orient_patches(patches, normals, out=None):
     return out, axis
 
 
+FPFH_WIDTH = 33
+
+
+def point_fpfh(workspace, n, points, normals, radius, return_spfh=False):
+    """(workspace from point_grid_build of the n points `points` f[n,3], normals f[n,3], float radius <= the build's max_radius)
+    -> (fpfh f[n,33], count int32 [n], flags int32 [n], spfh int32 [n,33] or None): the FPFH descriptor of every point of the
+    grid's own cloud over its in-radius neighbourhood (epn_point_fpfh_f32, include/epn_so3conv.h; no counterpart among the
+    reference's extensions -- it replaces open3d's compute_fpfh_feature of SPConvNets/datasets/preprocess/run_keypoint.py:40-50).
+    flags bit 0: no neighbour; bit 1: a non-finite coordinate or normal, or a point the grid leaves out; the row is zero with
+    either."""
+    from ...data import _tensor
+    lib = _lib.get_lib()
+    workspace = _tensor(workspace, "workspace", (None,), torch.int64)
+    n, r = int(n), float(radius)
+    points = _tensor(points, "points", (n, 3), torch.float32)
+    normals = _tensor(normals, "normals", (n, 3), torch.float32)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"radius must be finite and > 0, got {radius}")
+    if n > MAX_GRID_POINTS:
+        raise ValueError(f"a point grid takes at most 2^22 points, got {n}")
+    _lib.same_device(workspace, points, normals)
+    i32 = dict(dtype=torch.int32, device=points.device)
+    fpfh = torch.empty((n, FPFH_WIDTH), dtype=torch.float32, device=points.device)
+    count, flags = torch.empty((n,), **i32), torch.empty((n,), **i32)
+    spfh = torch.empty((n, FPFH_WIDTH), **i32) if return_spfh else None
+    ws_bytes = int(lib.epn_point_fpfh_workspace_bytes(n))
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=points.device)
+    _lib.check(lib.epn_point_fpfh_f32(ctypes.c_void_p(workspace.data_ptr()), n, _lib.dev_ptr(points, "points"),
+                                      _lib.dev_ptr(normals, "normals"), r, _lib.dev_ptr(fpfh, "fpfh"),
+                                      _lib.dev_ptr(count, "count", torch.int32), _lib.dev_ptr(flags, "flags", torch.int32),
+                                      _lib.dev_ptr(spfh, "spfh", torch.int32), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8,
+                                      _lib.stream_of(points)), "point_fpfh")
+    return fpfh, count, flags, spfh
+
+
 MAX_ICP_POINTS = 2 ** 20
 MAX_ICP_ITER = 1024
 ICP_FLAGS = ("bit 0: converged (the stop test was met)",

@@ -466,6 +466,57 @@ int epn_point_normals_f32(const void *workspace, int64_t n, const float *qry, in
 int epn_orient_patches_f32(const float *patches, const float *normals, int64_t k, int n_sample, float *axis, float *out,
                            epn_stream_t stream);
 
+/* FPFH descriptors (csrc/fpfh.hip, csrc/fpfh_math.h): the reference's compute_fpfh_feature
+ * (SPConvNets/datasets/preprocess/run_keypoint.py:40-50), which runs open3d's compute_fpfh_feature with KDTreeSearchParamRadius on
+ * the host.  The steps are open3d's ComputePairFeatures, ComputeSPFHFeature and ComputeFPFHFeature, made independent of the
+ * order of the neighbours.  It is argued from open3d's algorithm, not run against it: open3d is not installed where this was
+ * written.  The numpy restatement (tests/fpfh_ref.py) is the contract; it fixes the result, not the schedule.
+ *
+ * epn_point_fpfh_f32: the grid of a build (grid_workspace and n, as epn_point_grid_nn_f32 takes them), points f32[n,3] = the
+ *   cloud the grid was built from, normals f32[n,3], radius -> fpfh f32[n,33] row-major (open3d's .data.T), count i32[n],
+ *   flags i32[n] and, NULL-able, spfh i32[n,33].  The queries are always the grid's own points: a pair feature needs the query's
+ *   normal, so there is no foreign-query form.
+ *   neighbourhood   of point i: the grid's points k != i (by row) with d2 <= r2, d2 and r2 exactly as in epn_point_grid_nn_f32
+ *                   (individually rounded fp32, no fma, inclusive, r2 = (float)(radius * radius) from the fp64 product).  d2 is
+ *                   symmetric, so k is a neighbour of i exactly when i is one of k.  A duplicate at another row is a neighbour
+ *                   (d2 = 0).  used = the size of this set = count.  Radius search only (KDTreeSearchParamRadius, the
+ *                   reference's call); open3d's hybrid max_nn cut is not offered.
+ *   pair features   of (i, k), all in fp64 on the promoted fp32 inputs, every operation rounded on its own (no fma), dot products
+ *                   as (a0 b0 + a1 b1) + a2 b2, cross products as (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0):
+ *                   d = p_k - p_i, len = sqrt(d . d); len == 0: f = (0, 0, 0).  a1 = (n_i . d) / len, a2 = (n_k . d) / len.
+ *                   |a1| < |a2| (open3d: acos(|a1|) > acos(|a2|); the two differ only where acos rounds two arguments to one
+ *                   value, or for |a| > 1): n1 = n_k, n2 = n_i, d = -d, f3 = -a2; otherwise n1 = n_i, n2 = n_k, f3 = a1.
+ *                   v = d x n1; |v| == 0: f = (0, 0, 0); else v = v / |v|, w = n1 x v, f2 = v . n2, f1 = atan2(w . n2, n1 . n2)
+ *                   with a first argument of -0 taken as +0.  A normal (of i or of k) with a non-finite component: f = (0, 0, 0).
+ *   bins            h1 = floor((11 (f1 + pi)) / (2 pi)), h2 = floor((11 (f2 + 1)) 0.5), h3 = floor((11 (f3 + 1)) 0.5), each
+ *                   clamped to 0..10.  Every neighbour adds 1 to c_i(h1), c_i(11 + h2), c_i(22 + h3): spfh = c_i, integers.
+ *                   open3d's SPFH is 100 c_i(j) / used_i, which it reaches by adding 100 / used per neighbour in floating point.
+ *   fpfh            d2min = the smallest non-zero d2_k over the neighbours of i.  For every neighbour k with d2_k > 0,
+ *                   term_k(j) = rint(((d2min / d2_k) (c_k(j) / used_k)) 2^40): the two quotients and the product rounded once
+ *                   each, the scaling exact.  A(j) = sum_k term_k(j) and G(g) = the sum of A over the eleven bins of group g,
+ *                   both int64: integer sums do not depend on their order.  fpfh(j) = (float)((100 A(j)) / G(g) +
+ *                   (100 c_i(j)) / used_i), the first quotient 0 when G(g) == 0.  This is open3d's FPFH with its two deviations
+ *                   from the paper (the weight is 1 / d2, not 1 / d; the point's own SPFH is added after the normalisation to
+ *                   100); the common factor d2min cancels in A / G and is there to bound the terms: term <= 2^40, the eleven
+ *                   terms of one neighbour and group add up to at most 2^40 + 11, and n <= 2^22 keeps A and G below 2^63.
+ *   flags           bit 0: used == 0; the row is zero.  bit 1: a non-finite coordinate or normal component of the point, or a
+ *                   point the grid leaves out (ref_valid); the rows of fpfh and spfh are zero.  A point the grid leaves out is
+ *                   nobody's neighbour and has count = 0 (so bit 0 is set as well); a point in the grid whose normal is not
+ *                   finite keeps its count, stays a neighbour, and adds the features (0, 0, 0) to its neighbours' counts and
+ *                   nothing to their weighted sums.  Nothing asserts, and no point affects another beyond this.
+ *   Two launches, one wave per point and four per workgroup in both: the counts (per-wave integer histograms in LDS), then the
+ *   weighted sums (one bin per lane, one int64 each).  No floating-point atomics, no allocation, no host synchronisation: bitwise
+ *   repeatable and graph-capturable.
+ *   Workspace: epn_point_fpfh_workspace_bytes(n) bytes (host-only; 0 outside 0 <= n <= 2^22), 16-byte aligned, written by the
+ *   first launch: c i32[n,33] and d2min f32[n].
+ *   0 <= n <= 2^22, radius finite, 0 < radius <= max_radius of the build, a grid workspace address and n that a build has been
+ *   called with, and, when n > 0, points, normals, fpfh, count, flags and a large enough workspace: EPN_EINVAL otherwise, decided
+ *   before any HIP runtime call.  n == 0 succeeds and launches nothing. */
+size_t epn_point_fpfh_workspace_bytes(int64_t n);
+int epn_point_fpfh_f32(const void *grid_workspace, int64_t n, const float *points, const float *normals, double radius, float *fpfh,
+                       int32_t *count, int32_t *flags, int32_t *spfh, void *workspace, size_t workspace_bytes,
+                       epn_stream_t stream);
+
 /* ICP refinement: the dense alignment after epn_ransac_register_f64 (csrc/icp_refine.hip, csrc/icp_math.h).  This
  * is open3d's registration_icp with TransformationEstimationPointToPoint or TransformationEstimationPointToPlane and
  * ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration), made deterministic.  It is argued from open3d's
